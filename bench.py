@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Daft-Exprt hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run --nproc-per-node N
 ... bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE in the environment) or bench.py does it itself: with no
@@ -12,8 +12,24 @@ A "step" = one optimizer step of the full model (forward + 7-term loss + backwar
 dropout ON) on one synthetic batch per GPU of BASELINE.json configs[1]: 11 speakers, batch 48 per GPU, 80-bin mel,
 T <= 1000 frames (utterance 0 forced to 1000), bf16 MFMA operands / fp32 accumulate and master weights.
 Inputs are resident in HBM when the timed region starts.  value = valid mel frames (padding excluded) processed by
-ALL ranks per second.  Prints ONE JSON line (rank 0) carrying `roofline` (dominant kernel, live HIP-event timing)
-and `cpu_baseline` (the CPU oracle timed on this host, bounded sample).
+ALL ranks per second.  Prints ONE JSON line (rank 0).
+
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and
+the line, with `roofline` and `cpu_baseline` null.  --full also fills `roofline` (dominant kernel, live HIP-event timing over
+extra untimed steps) and `cpu_baseline` (the CPU oracle timed on this host, bounded sample) and, for the default 1-GPU train
+workload, adds the secondary objects (`train_16x3`, `fp32`, `c5`, `synth`); --no-probe / --no-cpu-baseline / --no-secondary
+switch those parts off again.
+
+The last timed step starts again from the seeded initial weights and optimizer state (an in-place copy of 177 MB, once
+per run): the gradient reductions accumulate with float atomics, so a trajectory of several steps is not reproducible (Adam's
+normalised update turns their last-bit differences into lr-sized ones, and the next steps grow them), while one step from a fixed
+state is -- its forward pass and loss bit for bit, its gradients to rounding.  Inputs, initial weights and dropout seeds are fixed
+by the arguments.
+
+--dump-outputs DIR: after the timed steps, what that last step gave its caller, as float32 .npy files: loss_terms.npy (the 8 loss
+terms: loss.KEYS, then the total), grad_norm_sq.npy (1,) and the model's predictions (`model.last_outputs`) speaker_logits.npy
+(B, speakers), durations.npy / energies.npy / pitches.npy (B, L) and mel.npy (B, 80, T), zero past each utterance's length
+(~15 MB at the default size).  Runs with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -278,7 +294,7 @@ def synth_bench(args, hp, dev, rank, world, emit=True, cpu_steps=(2, 5)):
     elapsed, utts, frames, flops = [float(v) for v in stats]
     peak = PEAK_MFMA_BF16 if args.dtype == 'bf16' else 157.3e12
     roofline = None
-    if not args.no_probe:
+    if args.full and not args.no_probe:
         ops.PROBE = {}
         nprobe = min(args.steps, 3)
         outl = []
@@ -311,7 +327,7 @@ def synth_bench(args, hp, dev, rank, world, emit=True, cpu_steps=(2, 5)):
                     'hbm': hbm_line(elapsed / args.steps * 1e3, 'synth_counters') if (B == 256 and args.dtype == 'bf16') else None}
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline_synth(hp, cpu_inputs, warmup=cpu_steps[0], steps=cpu_steps[1])
         line = ({'metric': 'synth-path mels/sec', 'value': utts / elapsed, 'unit': 'utterances/s', 'n_gpus': world,
                           'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
@@ -439,6 +455,26 @@ def secondary_train(dev, batch, accum, dtype, steps, warmup, pool=4, group=True,
                            'frac': done_flops / elapsed / peak}}
 
 
+def dump_outputs(out_dir, terms, gnorm_sq, outputs, inputs):
+    ''' --dump-outputs: what `Trainer.step` hands its caller -- the (8,) loss terms and the squared gradient norm -- and the predictions
+        of its forward pass (`model.last_outputs`), rows past each utterance's phoneme / frame count zeroed (their content is
+        unspecified), as float32 .npy files '''
+    import numpy as np
+    logits, _, (dur, energy, pitch), mel, _ = outputs
+    L, T = inputs[5].long(), inputs[9].long()
+
+    def valid(t, lengths, axis):   # zero past lengths[b] along `axis`
+        keep = torch.arange(t.shape[axis], device=t.device)[None, :] < lengths.to(t.device)[:, None]
+        return t.float() * keep.reshape(keep.shape[0], *[1] * (axis - 1), keep.shape[1], *[1] * (t.dim() - axis - 1))
+    arrays = {'loss_terms': terms, 'grad_norm_sq': gnorm_sq.reshape(1), 'speaker_logits': logits, 'durations': valid(dur, L, 1),
+              'energies': valid(energy, L, 1), 'pitches': valid(pitch, L, 1), 'mel': valid(mel, T, 2)}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, {k: a.nbytes for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+
+
 def spawn_ranks(n):
     ''' re-execute this command line as n ranks (one per GPU) under torch.distributed.run; rank 0 prints the JSON line '''
     import socket
@@ -462,15 +498,19 @@ def main():
     ap.add_argument('--batch', type=int, default=48)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--pool', type=int, default=4, help='distinct synthetic batches cycled through')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the roofline probe steps, the CPU oracle baseline and the secondary '
+                         'objects of the default line (--no-probe / --no-cpu-baseline / --no-secondary leave them out again)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy (train step workload)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-probe', action='store_true')
     ap.add_argument('--cpu-utts', type=int, default=8, help='utterances of the bench batch the cpu_baseline leg steps through (48 = the whole batch, '
-                    '~20 s per step: BASELINE.md 4; the default keeps the default run within a few minutes)')
+                    '~20 s per step: BASELINE.md 4; the default keeps a --full run within a few minutes)')
     ap.add_argument('--cpu-steps', type=int, default=3, help='timed steps of the cpu_baseline leg (after 1 warm-up)')
     ap.add_argument('--graph', action='store_true', help='replay each resident batch\'s step as ONE captured hipGraph (train.CapturedStep) instead of '
                     'launching its ~300 kernels from the host (measured: a tie at B = 48, see DESIGN 5)')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the extra objects of the default line ("synth" = configs[3] at 256 sentences, "train_16x3" = the reference\'s own '
+                    help='with --full: skip the extra objects of the default line ("synth" = configs[3] at 256 sentences, "train_16x3" = the reference\'s own '
                          '16 x 3 accumulation schedule, "fp32" = the exact-parity arithmetic); they only run for the default 1-GPU train workload')
     ap.add_argument('--workload', default='train', choices=['train', 'synth'],
                     help='train = BASELINE configs[1] (default; configs[4] with --batch 256 --tmin 500); synth = configs[3]')
@@ -479,6 +519,10 @@ def main():
                     help='step = Trainer.step back to back on resident batches (the metric); train = the REAL daft_exprt.train.train() loop '
                          '(DataLoader workers, collate, H2D, per-iteration logging) on synthetic utterances, 1 GPU')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and (args.workload != 'train' or args.loop != 'step'):
+        ap.error('--dump-outputs covers the train step workload (--workload train --loop step)')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus)
@@ -541,6 +585,8 @@ def main():
             dist.barrier()
 
     it = 20000   # adversarial weight at its maximum (>= warmup_steps): the GRL path is live
+    opt = trainer.optimizer          # the seeded initial state the last timed step starts from (see the module docstring)
+    initial = (model.flat_parameters().clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.step_count)
     if args.graph and trainer.captured is not None:          # set-up, like building the model: the hipGraph of each resident batch's step
         trainer.captured.auto = False                          # (one eager step to load the kernels, then the capture, which executes nothing)
         for b in batches:
@@ -556,12 +602,19 @@ def main():
     t0 = time.perf_counter()
     done_frames, done_flops = 0, 0.
     for k in range(args.steps):
-        trainer.step([batches[k % args.pool]], it + args.warmup + k)
+        if k == args.steps - 1:
+            for dst, src in zip((model.flat_parameters(), opt.exp_avg, opt.exp_avg_sq), initial):
+                dst.copy_(src)
+            opt.step_count = initial[3]
+            model.mark_updated()     # the operand copies of the weights are re-packed by the step
+        result = trainer.step([batches[k % args.pool]], it + args.warmup + k)
         done_frames += frames[k % args.pool]
         done_flops += flops[k % args.pool]
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # before any further step reuses the result buffers or moves the parameters
+        dump_outputs(args.dump_outputs, *result, model.last_outputs, batches[(args.steps - 1) % args.pool][0])
     if dist_on:
         # per-rank diagnostics of the FIRST multi-GPU record: the imbalance term of the scaling prediction (this rank's padded
         # sizes and valid frames: a rank whose T_max is larger runs a longer step and everyone waits for it in the collective) and the
@@ -588,7 +641,7 @@ def main():
 
     # ---- dominant-kernel roofline: live HIP-event timing of the conv-as-GEMM kernel over extra (untimed) steps
     roofline = None
-    if not args.no_probe:
+    if args.full and not args.no_probe:
         ops.PROBE = {}
         nprobe = min(args.steps, 4)
         for k in range(nprobe):
@@ -638,7 +691,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(hp, cpu_batches[0], n_utt=args.cpu_utts, steps=args.cpu_steps)
         out = {'metric': 'training mel-frames/sec', 'value': done_frames / elapsed, 'unit': 'mel-frames/s', 'n_gpus': world,
                'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
@@ -651,10 +704,10 @@ def main():
                           'params': model.n_params},
                'roofline': roofline, 'cpu_baseline': cpu}
         c2_default = args.batch == 48 and args.tmin == 1 and args.dtype == 'bf16' and world == 1
-        if c2_default and not args.no_secondary:
-            # the rest of BASELINE.json's metric and the schedules a user of the reference would run, from the SAME invocation (the driver
-            # only ever runs `python bench.py --gpus 1`): each is a complete timing of its own, none touches the headline fields above
-            del trainer, model, batches
+        if c2_default and args.full and not args.no_secondary:
+            # the rest of BASELINE.json's metric and the schedules a user of the reference would run, from the SAME invocation
+            # (`python bench.py --gpus 1 --full`): each is a complete timing of its own, none touches the headline fields above
+            del trainer, model, batches, opt, initial
             torch.cuda.empty_cache()
             out['train_16x3'] = secondary_train(dev, 16, 3, 'bf16', steps=15, warmup=6)
             seq = secondary_train(dev, 16, 3, 'bf16', steps=10, warmup=5, group=False)

@@ -9,7 +9,7 @@ OUT=gpurun_out/profiles_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 CMD="python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-probe --no-secondary"
-python bench.py --batch 256 --tmin 500 --steps 10 --warmup 15 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_train_c5.json 2> $OUT/bench.err
+python bench.py --full --batch 256 --tmin 500 --steps 10 --warmup 15 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_train_c5.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace -d $OUT/kt -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-probe --no-secondary > /dev/null 2> $OUT/kt.err
 DB=$(ls $OUT/kt/*/*.db | head -1)
 python tools/rocprof_stats.py $DB > $OUT/${TAG}_kernel_trace.md
@@ -40,13 +40,13 @@ rm -rf $OUT/pa1 $OUT/pa2
 # the bench lines of C2 / C4 LAST: bench.py quotes roofline.traffic / hbm from profiles/<tag>_counters.json only when that file was
 # recorded for the kernel build that is running, so the counters of THIS build go into profiles/ (of this box's copy) first
 cp $OUT/${TAG}_counters.json $OUT/${TAG}_synth_counters.json profiles/
-python bench.py > $OUT/${TAG}_bench.json 2>> $OUT/bench.err
-python bench.py --workload synth --batch 256 --steps 10 --warmup 3 > $OUT/${TAG}_bench_synth_c4.json 2>> $OUT/bench.err
+python bench.py --full > $OUT/${TAG}_bench.json 2>> $OUT/bench.err
+python bench.py --full --workload synth --batch 256 --steps 10 --warmup 3 > $OUT/${TAG}_bench_synth_c4.json 2>> $OUT/bench.err
 # the multi-rank code path on real RCCL through a one-rank world: what the process group, the per-bucket all-reduce
 # hooks and the per-bucket optimizer cost before any byte crosses xGMI
-DX_FORCE_DIST=1 python bench.py --no-secondary --no-cpu-baseline 2> $OUT/bench_rccl.err | grep "^{" > $OUT/${TAG}_bench_one_rank_rccl.json
+DX_FORCE_DIST=1 python bench.py --full --no-secondary --no-cpu-baseline 2> $OUT/bench_rccl.err | grep "^{" > $OUT/${TAG}_bench_one_rank_rccl.json
 grep "bench rank" $OUT/bench_rccl.err > $OUT/${TAG}_one_rank_rccl_reducer.txt
 # the CPU oracle on the WHOLE B = 48 bench batch, 1 warm-up + 5 timed steps (the default run keeps its 8-utterance sample)
-python bench.py --cpu-utts 48 --cpu-steps 5 --no-secondary --no-probe --steps 5 2>> $OUT/bench.err | python -c "import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(json.dumps(d['cpu_baseline'], indent=1))" > $OUT/${TAG}_cpu_baseline_full_batch.json
+python bench.py --full --cpu-utts 48 --cpu-steps 5 --no-secondary --no-probe --steps 5 2>> $OUT/bench.err | python -c "import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(json.dumps(d['cpu_baseline'], indent=1))" > $OUT/${TAG}_cpu_baseline_full_batch.json
 cat $OUT/counters_summary.txt
 head -c 400 $OUT/${TAG}_bench.json; echo

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Checkpoint interop against the reference's OWN code, run in the build container (where /root/reference exists; the test that
-calls this skips elsewhere -- nothing here travels to the GPU box):
+"""Checkpoint interop against the reference's OWN code, where a checkout of the reference is available (tools/gen_goldens.py
+REF_SRC); tests/test_reference_interop.py checks the same contract against the stored reference-written file instead:
 
   1. the reference's DaftExprt (default architecture, 11 speakers) takes two `torch.optim.Adam` steps (the reference trainer's
      settings, train.py:299-301) on synthetic gradients and writes a checkpoint with ITS `save_checkpoint` (train.py:56-78);
