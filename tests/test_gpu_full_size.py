@@ -99,8 +99,8 @@ def test_balanced_tiles_match_fixed_tiles_at_full_size():
 
 
 def test_tile_plans_are_rebuilt_for_every_batch():
-    ''' two different batches through the same model, back to back: the plan of the first (cached by the address of its
-        lengths tensor) must not survive into the second, whose lengths tensor may reuse that address '''
+    ''' two different batches through the same model, back to back: each batch must run on tile plans built from its own
+        lengths, never on those of the batch before '''
     import bench
     from daft_exprt.data_loader import synthetic_batch
     from daft_exprt.model import DaftExprt

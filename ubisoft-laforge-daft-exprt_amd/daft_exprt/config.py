@@ -2,7 +2,7 @@
 
 Only switches that select between TESTED paths, or that a measurement protocol of DESIGN.md names, are left; the A/B switches of
 rounds 1-4 whose verdicts are recorded in DESIGN section 9 ("not kept") are gone together with the code they guarded.  Tests flip
-the module attributes they exercise (`ops.USE_SPLITK`, `ops.USE_WIDE`, `ops.USE_FUSED_HEADS`, `ops.WGRAD_WORKSPACE`,
+the module attributes they exercise (`ops.USE_SPLITK`, `ops.USE_FUSED_HEADS`, `ops.WGRAD_WORKSPACE`,
 `model.balanced_tiles`, `model.fuse_ln_backward`, `optimizer.fuse_pack`); those have no environment form.
 
 | variable | default | effect |

@@ -136,6 +136,70 @@ class _Saved(object):
     ''' bag of activations kept by the forward pass for the hand-written backward pass '''
 
 
+class _Geometry(object):
+    ''' what the kernels of one pass need to know about one lengths tensor (B, N rows), built once per pass and handed down to
+        every stage that reads it (their saved records keep it for the backward pass):
+          skip, nmax  the `skip_lengths` argument and the per-utterance hard sequence end: inside a grouped step
+                      (`data_loader.GroupedBatch.bounds`) min(length, n_max - 2) of the utterance's own micro-batch and n_max (rows
+                      at or past it are written as zeros); else the lengths themselves and None
+          plan        balanced position tiles for the LayerNorm-fused k = 3 GEMMs (`ops.conv_tile_plan`), bf16 with
+                      `balanced_tiles` only (else None)
+          order       longest-first launch order of the attention kernels (`ops.length_order`), B >= 2 only (else None)
+          wide        balanced tiles for the wide pre-net / predictor GEMMs (`dx_conv1d_wide`, halo 2, tile count a multiple of 64),
+                      bf16 only (else None)
+        plan, order and -- outside a grouped step -- wide come from ONE launch (`ops.batch_prep`).  In a grouped step wide is built
+        from skip on first use, on the stream current then. '''
+
+    def __init__(self, model, lengths, N, bounds=None):
+        self.lengths, self.N = lengths, N
+        self.skip, self.nmax = (lengths, None) if bounds is None else bounds
+        self._bf = model.cd == torch.bfloat16
+        plan, wide, order = self._bf and model.balanced_tiles, self._bf and bounds is None, lengths.shape[0] >= 2
+        self.plan = self._wide = self.order = None
+        if lengths.is_cuda and (self._bf or order):
+            self.plan, self._wide, self.order = ops.batch_prep(lengths, N, plan, wide, order)
+
+    @property
+    def wide(self):
+        if self._wide is None and self._bf:
+            self._wide = ops.conv_tile_plan(self.skip, self.N, halo=2, round_to=64)
+        return self._wide
+
+
+# the events of the work the training step hands to the weight-gradient stream (see `DaftExprt.overlap_predictor`): the forks, in
+# pass order, and the points the launch stream joins back at ('... done')
+_HANDOFFS = ('classifier fwd', 'predictor fwd', 'predictor fwd done', 'predictor bwd', 'predictor bwd done', 'classifier bwd done',
+             'upsampler grads', 'embedding grad')
+
+
+class _Beside(object):
+    ''' `with _Beside(side, events, name) as fork:` runs the body on stream `side` behind everything the current stream has issued
+        so far (events[name] recorded there, waited for on `side`), or in line when `side` is None.  `fork.mark(done)` records
+        events[done] on `side`, where the launch stream joins later.  A plain class rather than a generator-based context manager:
+        it sits in the host-bound phoneme-level stretches of the step. '''
+    __slots__ = ('side', 'events', 'name', 'ctx')
+
+    def __init__(self, side, events, name):
+        self.side, self.events, self.name = side, events, name
+
+    def __enter__(self):
+        if self.side is not None:
+            ev = self.events[self.name]
+            ev.record()
+            self.side.wait_event(ev)
+            self.ctx = torch.cuda.stream(self.side)
+            self.ctx.__enter__()
+        return self
+
+    def mark(self, done):
+        if self.side is not None:
+            self.events[done].record(self.side)
+
+    def __exit__(self, *exc):
+        if self.side is not None:
+            self.ctx.__exit__(*exc)
+
+
 class _Bridge(torch.autograd.Function):
     ''' one autograd node for the whole model: lets `loss.backward()` (reference train loop, train.py:391)
         drive the hand-written backward pass; parameter gradients are written into the flat buffer. '''
@@ -205,10 +269,8 @@ class DaftExprt(nn.Module):
         self._hop = None
         self._side_deferred = None
         self.fuse_ln_backward = True   # see _fft_block_bwd (tests compare against the separate LayerNorm-backward launches)
-        self.balanced_tiles = True     # see _plan (tests compare against the fixed-tile launches)
-        self._plans = {}
-        self._hard = {}
-        self.attn_lpt = True           # see _order
+        self.balanced_tiles = True     # see _Geometry.plan (tests compare against the fixed-tile launches)
+        self._geometry = ()            # the _Geometry records of the latest pass: their plan buffers live until the next pass starts
         # the local prosody predictor beside the decoder: in a teacher-forced step its forward feeds nothing but the loss and its backward
         # needs nothing but the loss gradients, so both run on the weight-gradient stream (idle in the forward pass, a FIFO of launches
         # that nobody waits for in the backward pass) while the launch stream goes on with upsampling and decoder.  The same holds for
@@ -216,7 +278,7 @@ class DaftExprt(nn.Module):
         # (Gaussian upsampling's three, the symbol embedding's): ~45 launches of 5-30 us off the critical path, 6.51 -> 6.34 ms per
         # step.  False: everything in line, as before (tests compare the two)
         self.overlap_predictor = True
-        self._pp_ev = None
+        self._handoff = None
         self._step_id, self._site, self._rank, self._capture_step0 = 0, 0, 0, 0
         self._seed_log = None
         self._trace = None    # tests set this to a list: every stage appends (kind, names, input, film, lengths, output)
@@ -404,68 +466,6 @@ class DaftExprt(nn.Module):
             return
         self._packed_version = self._dgrad_version = version
 
-    def _plan(self, lengths, N):
-        ''' balanced position tiles of this step's batch for the LayerNorm-fused k = 3 GEMMs (`ops.conv_tile_plan`): one
-            small launch per distinct lengths tensor per step, shared by the 8 forward and 8 backward launches that read it.
-            Frame-level stacks only: a phoneme-level batch is too small for the tile count to matter. '''
-        if not self.balanced_tiles or self.cd != torch.bfloat16 or lengths is None:
-            return None
-        key = (lengths.data_ptr(), N)
-        hit = self._plans.get(key)
-        if hit is None or hit[0] is not lengths:      # the entry keeps `lengths` alive, so its address cannot be recycled under the key
-            hit = self._plans[key] = (lengths, ops.conv_tile_plan(lengths, N))
-        return hit[1]
-
-    def _plan_wide(self, lengths, N):
-        ''' balanced tiles for the wide pre-net GEMMs (`dx_conv1d_wide`): rows < length + 2, tile count a multiple of 64 '''
-        if self.cd != torch.bfloat16 or lengths is None:
-            return None
-        key = ('wide', lengths.data_ptr(), N)
-        hit = self._plans.get(key)
-        if hit is None or hit[0] is not lengths:
-            hit = self._plans[key] = (lengths, ops.conv_tile_plan(lengths, N, halo=2, round_to=64))
-        return hit[1]
-
-    def _prep(self, lengths, N):
-        ''' the tile plans and the attention launch order of one lengths tensor from ONE launch (`ops.batch_prep`) instead of
-            up to three lazy ones (`_plan`, `_plan_wide`, `_order` then find their entries) '''
-        if lengths is None or not lengths.is_cuda:
-            return
-        bf, B = self.cd == torch.bfloat16, lengths.shape[0]
-        plan = bf and self.balanced_tiles
-        order = self.attn_lpt and B >= 2
-        if not (plan or bf or order):
-            return
-        wide = bf and self._skip(lengths) is lengths   # (grouped step: the halo-2 plan is built from the skip tensor, lazily, by `_plan_wide`)
-        p0, p2, od = ops.batch_prep(lengths, N, plan, wide, order)
-        if plan:
-            self._plans[(lengths.data_ptr(), N)] = (lengths, p0)
-        if wide:
-            self._plans[('wide', lengths.data_ptr(), N)] = (lengths, p2)
-        if order:
-            self._plans[('order', lengths.data_ptr())] = (lengths, od)
-
-    def _order(self, lengths):
-        ''' longest-first launch order of the attention kernels (`ops.length_order`), one per distinct lengths tensor per step '''
-        if not self.attn_lpt or lengths.shape[0] < 2:
-            return None
-        key = ('order', lengths.data_ptr())
-        hit = self._plans.get(key)
-        if hit is None or hit[0] is not lengths:
-            hit = self._plans[key] = (lengths, ops.length_order(lengths))
-        return hit[1]
-
-    def _skip(self, lengths):
-        ''' the `skip_lengths` argument for this lengths tensor: the tensor itself, or -- inside a grouped step
-            (`data_loader.GroupedBatch`) -- min(length, n_max - 2) of the utterance's own micro-batch '''
-        hit = self._hard.get(lengths.data_ptr()) if lengths is not None else None
-        return lengths if hit is None else hit[0]
-
-    def _nmax(self, lengths):
-        ''' per-utterance hard sequence end of a grouped step (rows at or past it are written as zeros), else None '''
-        hit = self._hard.get(lengths.data_ptr()) if lengths is not None else None
-        return None if hit is None else hit[1]
-
     def set_rank(self, rank):
         ''' data-parallel rank of this replica: folded into every dropout seed so that the ranks draw independent masks
             (torch's per-process Philox streams in the reference are independent as well) '''
@@ -537,7 +537,7 @@ class DaftExprt(nn.Module):
             [mel, output_lengths], weights
 
     # ------------------------------------------------------------------ forward building blocks
-    def _fft_block_fwd(self, W, pre, x, film, lengths, cfg, train, save, x_lp=None, qkv=None, next_pre=None):
+    def _fft_block_fwd(self, W, pre, x, film, g, cfg, train, save, x_lp=None, qkv=None, next_pre=None):
         ''' one FFT block (`model.py:251-264`).  In bf16 mode the LayerNorm kernels also emit bf16 copies of their
             outputs (`*_lp`): they are what the following GEMMs read (half the bytes, no in-kernel conversion) --
             numerically identical to casting at operand-load time.  qkv: this block's QKV projection when the block below has
@@ -553,17 +553,17 @@ class DaftExprt(nn.Module):
         xin = x_lp if x_lp is not None else x
         if qkv is None:
             qkv = ops.conv1d(xin, W[f'{a_pre}.multi_head_attention.in_proj_weight'], P[f'{a_pre}.multi_head_attention.in_proj_bias'],
-                             out_dtype=cd, skip_lengths=self._skip(lengths))
-        o, lse = ops.attention_fwd(qkv, lengths, cfg['attn_nb_heads'], p_attn, seeds[0], need_lse=save, order=self._order(lengths))
+                             out_dtype=cd, skip_lengths=g.skip)
+        o, lse = ops.attention_fwd(qkv, g.lengths, cfg['attn_nb_heads'], p_attn, seeds[0], need_lse=save, order=g.order)
         # out-projection + Dropout + residual + LayerNorm + mask in ONE launch (the GEMM tile holds complete 128-ch rows)
         # (training, bf16, split-K FF kernel: the fp32 copy of `a` has ONE reader, the residual add of the FF LayerNorm, which re-derives it
         #  from s1 and the row statistics -- ops.conv1d_ln `residual_ln`; `a` itself is then never stored)
-        wc2, plan = W[f'{f_pre}.convs.2.conv.weight'], self._plan(lengths, x.shape[1])
+        wc2, plan = W[f'{f_pre}.convs.2.conv.weight'], g.plan
         virt = bool(save and lp and config.VIRTUAL_RESIDUAL and self._trace is None and plan is not None and
                     ops.splitk_ln_ok(x.shape[0], x.shape[1], cd, wc2, plan, W.get(f'F:{f_pre}.convs.2.conv.weight')))
         a, a_lp, s1, mean1, rstd1 = ops.conv1d_ln(o, W[f'{a_pre}.multi_head_attention.out_proj.weight'],
                                                   P[f'{a_pre}.multi_head_attention.out_proj.bias'], x, P[f'{a_pre}.layer_norm.weight'],
-                                                  P[f'{a_pre}.layer_norm.bias'], lengths, save=save, p_pre=p_attn, seed_pre=seeds[1],
+                                                  P[f'{a_pre}.layer_norm.bias'], g.lengths, save=save, p_pre=p_attn, seed_pre=seeds[1],
                                                   lp_copy=lp, store_y=not virt)
         ain = a_lp if lp else a
         # (grouped step: the FF hidden is the one unmasked tensor whose row AT the sequence end reaches valid outputs -- mask it there)
@@ -572,34 +572,36 @@ class DaftExprt(nn.Module):
         wc0 = W[f'{f_pre}.convs.0.conv.weight']
         if save and config.RELU_BITS and ops.relu_bits_ok(ain, wc0, cd):
             h, hbits = ops.conv1d(ain, wc0, P[f'{f_pre}.convs.0.conv.bias'], out_dtype=cd, relu=True, relu_bits=True,
-                                  skip_lengths=self._skip(lengths), mask_lengths=self._nmax(lengths), w_frag=W.get(f'F:{f_pre}.convs.0.conv.weight'))
+                                  skip_lengths=g.skip, mask_lengths=g.nmax, w_frag=W.get(f'F:{f_pre}.convs.0.conv.weight'))
         else:
             h = ops.conv1d(ain, wc0, P[f'{f_pre}.convs.0.conv.bias'], out_dtype=cd, relu=True,
-                           skip_lengths=self._skip(lengths), mask_lengths=self._nmax(lengths), w_frag=W.get(f'F:{f_pre}.convs.0.conv.weight'))
+                           skip_lengths=g.skip, mask_lengths=g.nmax, w_frag=W.get(f'F:{f_pre}.convs.0.conv.weight'))
         # second FF conv + Dropout + residual + LayerNorm + FiLM + mask in ONE launch
         nmha = f'{next_pre}.attention.multi_head_attention' if (next_pre is not None and lp) else None
         u, u_lp, s2, mean2, rstd2, qkv_next = ops.conv1d_ln(
             h, wc2, P[f'{f_pre}.convs.2.conv.bias'], s1 if virt else a, P[f'{f_pre}.layer_norm.weight'], P[f'{f_pre}.layer_norm.bias'],
-            lengths, film=film, save=save, p_pre=p_conv, seed_pre=seeds[2], lp_copy=lp, plan=plan,
+            g.lengths, film=film, save=save, p_pre=p_conv, seed_pre=seeds[2], lp_copy=lp, plan=plan,
             residual_ln=(mean1, rstd1, P[f'{a_pre}.layer_norm.weight'], P[f'{a_pre}.layer_norm.bias']) if virt else None,
             w_frag=W.get(f'F:{f_pre}.convs.2.conv.weight'), w2_packed=W[f'{nmha}.in_proj_weight'] if nmha else None,
             b2=P[f'{nmha}.in_proj_bias'] if nmha else None) + ((None,) if nmha is None else ())
         if save:
-            s.pre, s.cfg, s.x, s.film, s.lengths = pre, cfg, xin, film, lengths
+            s.pre, s.cfg, s.x, s.film, s.lengths, s.geo = pre, cfg, xin, film, g.lengths, g
             s.qkv, s.o, s.lse, s.s1, s.mean1, s.rstd1, s.a, s.h, s.s2, s.mean2, s.rstd2 = qkv, o, lse, s1, mean1, rstd1, ain, h, s2, mean2, rstd2
             s.seeds, s.p_attn, s.p_conv = seeds, p_attn, p_conv
             s.hbits = hbits
         if self._trace is not None:
-            self._trace.append(('fft_block', pre, x, film, lengths, (a, u)))
+            self._trace.append(('fft_block', pre, x, film, g.lengths, (a, u)))
         return u, u_lp, s, qkv_next
 
-    def _conv_ln_fwd(self, W, conv_name, ln_name, x, p_drop, out_dtype, save, film=None, lengths=None, skip=None):
-        ''' conv k3 -> ReLU -> LayerNorm -> Dropout [-> FiLM -> mask]  (prenet `model.py:341-363`, predictor 528-566) '''
+    def _conv_ln_fwd(self, W, conv_name, ln_name, x, p_drop, out_dtype, save, g, film=None, masked=False, wgrad_lengths=None):
+        ''' conv k3 -> ReLU -> LayerNorm -> Dropout [-> FiLM -> mask]  (prenet `model.py:341-363`, predictor 528-566).  masked: rows past
+            g.lengths are zeroed; wgrad_lengths: the lengths argument of the weight gradient in the backward pass '''
         P = self._P
+        lengths, skip = g.lengths if masked else None, g.skip
         cout = P[f'{conv_name}.conv.weight'].shape[0]
         c_dtype = torch.float32 if (self.cd == torch.float32 or cout == 128) else self.cd   # wide tensors in the MFMA operand type
         c = ops.conv1d(x, W[f'{conv_name}.conv.weight'], P[f'{conv_name}.conv.bias'], relu=True, out_dtype=c_dtype, skip_lengths=skip,
-                       w_frag=W.get(f'F:{conv_name}.conv.weight'), wide_plan=self._plan_wide(skip, x.shape[1]) if f'F:{conv_name}.conv.weight' in W else None)
+                       w_frag=W.get(f'F:{conv_name}.conv.weight'), wide_plan=g.wide if f'F:{conv_name}.conv.weight' in W else None)
         seed = self._seed('behind LayerNorm')
         y, _, mean, rstd = ops.layernorm_fwd(c, P[f'{ln_name}.weight'], P[f'{ln_name}.bias'], film=film, lengths=lengths,
                                              out_dtype=out_dtype, save=save, p_post=p_drop, seed_post=seed, skip_lengths=skip)
@@ -608,11 +610,12 @@ class DaftExprt(nn.Module):
             s = _Saved()
             s.conv_name, s.ln_name, s.x, s.c, s.mean, s.rstd, s.p, s.seed, s.film, s.lengths, s.skip = \
                 conv_name, ln_name, x, c, mean, rstd, p_drop, seed, film, lengths, skip
+            s.geo, s.wgrad_lengths = g, wgrad_lengths
         if self._trace is not None:
             self._trace.append(('conv_ln', (conv_name, ln_name, skip), x, film, lengths, y))
         return y, s
 
-    def _prosody_encoder_fwd(self, W, frames_energy, frames_pitch, mel_specs, speaker_ids, output_lengths, train, save):
+    def _prosody_encoder_fwd(self, W, frames_energy, frames_pitch, mel_specs, speaker_ids, g, train, save):
         ''' `model.py:391-464` '''
         P, hp, cfg, pre = self._P, self.hp, self.hp.prosody_encoder, 'prosody_encoder'
         p_conv = cfg['conv_dropout'] if train else 0.
@@ -621,11 +624,10 @@ class DaftExprt(nn.Module):
         # = the rounding the first conv applies at operand load; its weight gradient (the last launch of the backward pass, nothing
         # left to hide it under) then runs on the LDS-DMA ring kernel
         x = ops.transpose_last2(mel_specs.float().contiguous(), torch.bfloat16 if self.cd == torch.bfloat16 else torch.float32)
-        wide = self.cd
-        skip = self._skip(output_lengths)
-        l1, s.c1 = self._conv_ln_fwd(W, f'{pre}.convs.0', f'{pre}.convs.2', x, p_conv, wide, save, skip=skip)
-        l2, s.c2 = self._conv_ln_fwd(W, f'{pre}.convs.4', f'{pre}.convs.6', l1, p_conv, wide, save, skip=skip)
-        l3, s.c3 = self._conv_ln_fwd(W, f'{pre}.convs.8', f'{pre}.convs.10', l2, p_conv, torch.float32, save, skip=skip)
+        wide, output_lengths = self.cd, g.lengths
+        l1, s.c1 = self._conv_ln_fwd(W, f'{pre}.convs.0', f'{pre}.convs.2', x, p_conv, wide, save, g, wgrad_lengths=output_lengths)
+        l2, s.c2 = self._conv_ln_fwd(W, f'{pre}.convs.4', f'{pre}.convs.6', l1, p_conv, wide, save, g, wgrad_lengths=output_lengths)
+        l3, s.c3 = self._conv_ln_fwd(W, f'{pre}.convs.8', f'{pre}.convs.10', l2, p_conv, torch.float32, save, g, wgrad_lengths=output_lengths)
         x0 = ops.scalar_embed_fwd([frames_energy, frames_pitch],
                                   [P[f'{pre}.energy_embedding.conv.weight'], P[f'{pre}.pitch_embedding.conv.weight']],
                                   [P[f'{pre}.energy_embedding.conv.bias'], P[f'{pre}.pitch_embedding.conv.bias']],
@@ -633,7 +635,7 @@ class DaftExprt(nn.Module):
         s.blocks = []
         x_lp = qkv = None
         for blk in range(cfg['nb_blocks']):
-            x0, x_lp, sb, qkv = self._fft_block_fwd(W, f'{pre}.blocks.{blk}', x0, None, output_lengths, cfg, train, save, x_lp, qkv,
+            x0, x_lp, sb, qkv = self._fft_block_fwd(W, f'{pre}.blocks.{blk}', x0, None, g, cfg, train, save, x_lp, qkv,
                                                     f'{pre}.blocks.{blk + 1}' if blk + 1 < cfg['nb_blocks'] else None)
             s.blocks.append(sb)
         emb = ops.masked_mean_fwd(x0, output_lengths)
@@ -670,31 +672,31 @@ class DaftExprt(nn.Module):
         logits = ops.linear_small_fwd(h2, P[f'{pre}.5.linear_layer.weight'], P[f'{pre}.5.linear_layer.bias'])
         return logits, (emb, h1, h2)
 
-    def _phoneme_encoder_fwd(self, W, symbols, film, input_lengths, train, save):
+    def _phoneme_encoder_fwd(self, W, symbols, film, g, train, save):
         ''' `model.py:490-509` '''
         cfg, pre = self.hp.phoneme_encoder, 'phoneme_encoder'
-        x = ops.embed_pos_fwd(symbols, self._P[f'{pre}.symbols_embedding.weight'], self._pos_table(), input_lengths)
+        x = ops.embed_pos_fwd(symbols, self._P[f'{pre}.symbols_embedding.weight'], self._pos_table(), g.lengths)
         blocks, x_lp, qkv = [], None, None
         for blk in range(cfg['nb_blocks']):
-            x, x_lp, sb, qkv = self._fft_block_fwd(W, f'{pre}.blocks.{blk}', x, film[:, blk, :], input_lengths, cfg, train, save, x_lp, qkv,
+            x, x_lp, sb, qkv = self._fft_block_fwd(W, f'{pre}.blocks.{blk}', x, film[:, blk, :], g, cfg, train, save, x_lp, qkv,
                                                    f'{pre}.blocks.{blk + 1}' if blk + 1 < cfg['nb_blocks'] else None)
             blocks.append(sb)
         return x, blocks
 
-    def _predictor_fwd(self, W, enc, film, input_lengths, train, save):
+    def _predictor_fwd(self, W, enc, film, g, train, save):
         ''' `model.py:549-575` (nb_blocks = 1 in every published config; more blocks chain the same pattern) '''
         cfg, pre, P = self.hp.local_prosody_predictor, 'prosody_predictor', self._P
         p = cfg['conv_dropout'] if train else 0.
         x, saved = enc, []
         for blk in range(cfg['nb_blocks']):
-            x, s1 = self._conv_ln_fwd(W, f'{pre}.blocks.{blk}.0', f'{pre}.blocks.{blk}.2', x, p, self.cd, save, skip=self._skip(input_lengths))
+            x, s1 = self._conv_ln_fwd(W, f'{pre}.blocks.{blk}.0', f'{pre}.blocks.{blk}.2', x, p, self.cd, save, g)
             last = blk == cfg['nb_blocks'] - 1
             x, s2 = self._conv_ln_fwd(W, f'{pre}.blocks.{blk}.4', f'{pre}.blocks.{blk}.6', x, p, torch.float32 if last else self.cd,
-                                      save, film=film[:, blk, :], lengths=input_lengths if last else None, skip=self._skip(input_lengths))
+                                      save, g, film=film[:, blk, :], masked=last)
             saved.append((s1, s2))
         L = x.shape[1]
         y = ops.linear_small_fwd(x, P[f'{pre}.projection.linear_layer.weight'], P[f'{pre}.projection.linear_layer.bias'],
-                                 mask_lengths=input_lengths, N=L)
+                                 mask_lengths=g.lengths, N=L)
         return y, (saved, x, y)
 
     def _gu_params(self):
@@ -717,18 +719,18 @@ class DaftExprt(nn.Module):
             s.durations_float, s.energies, s.pitch, s.input_lengths, s.output_lengths = durations_float, energies, pitch, input_lengths, output_lengths
         return dec_in, weights, totals, s
 
-    def _decoder_fwd(self, W, x, film, output_lengths, train, save):
+    def _decoder_fwd(self, W, x, film, g, train, save):
         ''' `model.py:689-710` (positional add + mask already applied by the upsampling kernel) '''
         cfg, pre, P = self.hp.frame_decoder, 'frame_decoder', self._P
         blocks, x_lp, qkv = [], None, None
         for blk in range(cfg['nb_blocks']):
-            x, x_lp, sb, qkv = self._fft_block_fwd(W, f'{pre}.blocks.{blk}', x, film[:, blk, :], output_lengths, cfg, train, save, x_lp, qkv,
+            x, x_lp, sb, qkv = self._fft_block_fwd(W, f'{pre}.blocks.{blk}', x, film[:, blk, :], g, cfg, train, save, x_lp, qkv,
                                                    f'{pre}.blocks.{blk + 1}' if blk + 1 < cfg['nb_blocks'] else None)
             blocks.append(sb)
         mel = ops.conv1d(x, W[f'{pre}.projection.linear_layer.weight'], P[f'{pre}.projection.linear_layer.bias'],
-                         out_dtype=torch.float32, mask_lengths=output_lengths, transposed_out=True, skip_lengths=output_lengths)
+                         out_dtype=torch.float32, mask_lengths=g.lengths, transposed_out=True, skip_lengths=g.lengths)
         if self._trace is not None:
-            self._trace.append(('mel_projection', f'{pre}.projection.linear_layer', x, None, output_lengths, mel))
+            self._trace.append(('mel_projection', f'{pre}.projection.linear_layer', x, None, g.lengths, mel))
         return mel, (blocks, x)
 
     def _forward(self, inputs, train, save, bounds=None):
@@ -737,40 +739,29 @@ class DaftExprt(nn.Module):
         ops.H.require_gpu(symbols, mel_specs)
         self._step_id += 1
         self._site = 0
-        self._plans = {}
-        self._hard = {}
-        if bounds is not None:    # grouped micro-batches (`data_loader.GroupedBatch`): per-utterance hard sequence ends
-            skip_in, nmax_in, skip_out, nmax_out = bounds
-            self._hard = {input_lengths.data_ptr(): (skip_in, nmax_in), output_lengths.data_ptr(): (skip_out, nmax_out)}
-        self._prep(output_lengths, mel_specs.shape[2])
-        self._prep(input_lengths, symbols.shape[1])
+        # grouped micro-batches (`data_loader.GroupedBatch`): bounds = per-utterance hard sequence ends of the input and output lengths
+        g_out = _Geometry(self, output_lengths, mel_specs.shape[2], None if bounds is None else bounds[2:])
+        g_in = _Geometry(self, input_lengths, symbols.shape[1], None if bounds is None else bounds[:2])
+        self._geometry = (g_out, g_in)
         W = self._weights(need_dgrad=save)
         S = _Saved() if save else None
-        emb, films, s_pe = self._prosody_encoder_fwd(W, frames_energy, frames_pitch, mel_specs, speaker_ids, output_lengths, train, save)
+        emb, films, s_pe = self._prosody_encoder_fwd(W, frames_energy, frames_pitch, mel_specs, speaker_ids, g_out, train, save)
         beside = self._predictor_beside()
-        if beside:      # the speaker classifier feeds nothing but the loss either: the launch stream waits for it together with the predictor
-            main, side = torch.cuda.current_stream(), self.ensure_side_stream()
-            self._pp_ev[7].record(main)
-            side.wait_event(self._pp_ev[7])
-            with torch.cuda.stream(side):
-                logits, s_cls = self._classifier_fwd(emb)
-        else:
+        side = self.ensure_side_stream() if beside else None
+        # the speaker classifier feeds nothing but the loss either: the launch stream waits for it together with the predictor
+        with _Beside(side, self._handoff, 'classifier fwd'):
             logits, s_cls = self._classifier_fwd(emb)
-        enc, s_enc = self._phoneme_encoder_fwd(W, symbols, films[0], input_lengths, train, save)
-        if beside:
-            self._pp_ev[0].record(main)
-            side.wait_event(self._pp_ev[0])
-            with torch.cuda.stream(side):
-                y, s_pp = self._predictor_fwd(W, enc, films[1], input_lengths, train, save)
-                self._pp_ev[1].record(side)
-        else:
-            y, s_pp = self._predictor_fwd(W, enc, films[1], input_lengths, train, save)
+        enc, s_enc = self._phoneme_encoder_fwd(W, symbols, films[0], g_in, train, save)
+        with _Beside(side, self._handoff, 'predictor fwd') as fork:
+            y, s_pp = self._predictor_fwd(W, enc, films[1], g_in, train, save)
+            fork.mark('predictor fwd done')
         T = mel_specs.shape[2]
         dec_in, weights, _, s_gu = self._upsample_fwd(enc, durations_float, durations_int, symbols_energy, symbols_pitch,
                                                       input_lengths, output_lengths, T, save)
-        mel, s_dec = self._decoder_fwd(W, dec_in, films[2], output_lengths, train, save)
+        mel, s_dec = self._decoder_fwd(W, dec_in, films[2], g_out, train, save)
         if beside:
-            main.wait_event(self._pp_ev[1])
+            main = torch.cuda.current_stream()
+            main.wait_event(self._handoff['predictor fwd done'])
             # allocated on the side stream, consumed on the launch stream (the loss, `last_outputs`, user code): tell the caching allocator
             # (the saved activations stay in `_wgrad_keep` until the streams have joined at the end of the backward pass)
             logits.record_stream(main)
@@ -786,8 +777,8 @@ class DaftExprt(nn.Module):
             being captured (the capture's fork bookkeeping is `_flush_wgrads`'s), not under a stage trace, not without that stream '''
         ok = bool(self.overlap_predictor and config.WGRAD_SIDE_STREAM and ops.STEP_PTR is None and self._trace is None and
                   self._trace_bwd is None and self._flat is not None and self._flat.is_cuda)
-        if ok and self._pp_ev is None:
-            self._pp_ev = [torch.cuda.Event() for _ in range(8)]
+        if ok and self._handoff is None:
+            self._handoff = {name: torch.cuda.Event() for name in _HANDOFFS}
         return ok
 
     def _classifier_bwd(self, S, d_spk, zeros):
@@ -946,7 +937,7 @@ class DaftExprt(nn.Module):
         cap_in = ds2.clone() if self._trace_bwd is not None else None   # dL/d(s2 of this block): the residual gradient is updated in place below
         da = ds2
         self._wgrad(dz, s.h, G[f'{f_pre}.convs.2.conv.weight'], G[f'{f_pre}.convs.2.conv.bias'], s.lengths)
-        dh = ops.conv1d(dz, W[f'T:{f_pre}.convs.2.conv.weight'], None, out_dtype=cd, relu_gate=s.hbits if s.hbits is not None else s.h, skip_lengths=self._skip(s.lengths),
+        dh = ops.conv1d(dz, W[f'T:{f_pre}.convs.2.conv.weight'], None, out_dtype=cd, relu_gate=s.hbits if s.hbits is not None else s.h, skip_lengths=s.geo.skip,
                         w_frag=W.get(f'FT:{f_pre}.convs.2.conv.weight'))
         self._wgrad(dh, s.a, G[f'{f_pre}.convs.0.conv.weight'], G[f'{f_pre}.convs.0.conv.bias'], s.lengths)
         mha = f'{a_pre}.multi_head_attention'
@@ -956,7 +947,7 @@ class DaftExprt(nn.Module):
             dproj, d_o = ops.conv1d_lnbwd(dh, W[f'T:{f_pre}.convs.0.conv.weight'], da, s.s1, s.mean1, s.rstd1,
                                           P[f'{a_pre}.layer_norm.weight'], P[f'{a_pre}.layer_norm.bias'], s.lengths,
                                           G[f'{a_pre}.layer_norm.weight'], G[f'{a_pre}.layer_norm.bias'], p_pre=s.p_attn, seed_pre=s.seeds[1],
-                                          plan=self._plan(s.lengths, dh.shape[1]), w_frag=W.get(f'FT:{f_pre}.convs.0.conv.weight'),
+                                          plan=s.geo.plan, w_frag=W.get(f'FT:{f_pre}.convs.0.conv.weight'),
                                           w2_packed=W[f'T:{mha}.out_proj.weight'])
             ds1 = da
         else:
@@ -968,7 +959,7 @@ class DaftExprt(nn.Module):
         self._wgrad(dproj, s.o, G[f'{mha}.out_proj.weight'], G[f'{mha}.out_proj.bias'], s.lengths)
         if d_o is None:
             d_o = ops.conv1d(dproj, W[f'T:{mha}.out_proj.weight'], None, out_dtype=cd, skip_lengths=s.lengths)
-        dqkv = ops.attention_bwd(s.qkv, s.o, d_o, s.lse, s.lengths, s.cfg['attn_nb_heads'], s.p_attn, s.seeds[0], order=self._order(s.lengths))
+        dqkv = ops.attention_bwd(s.qkv, s.o, d_o, s.lse, s.lengths, s.cfg['attn_nb_heads'], s.p_attn, s.seeds[0], order=s.geo.order)
         self._wgrad(dqkv, s.x, G[f'{mha}.in_proj_weight'], G[f'{mha}.in_proj_bias'], s.lengths)
         if fuse and below is not None:
             fb = f'{below.pre}.feed_forward'
@@ -986,7 +977,7 @@ class DaftExprt(nn.Module):
             self._trace_bwd.append(('fft_block', s, None, cap_in, dx.clone()))
         return dx, None
 
-    def _conv_ln_bwd(self, W, s, dy, dfilm=None, need_dx=True, dx_out=None, lengths_hint=None):
+    def _conv_ln_bwd(self, W, s, dy, dfilm=None, need_dx=True, dx_out=None):
         ''' backward of `_conv_ln_fwd`; returns grad wrt its input (dtype = the input's) '''
         P, G = self._P, self._G
         # dc only feeds GEMMs (weight and data gradient): emit it in the MFMA operand type (= rounding at operand load)
@@ -996,11 +987,11 @@ class DaftExprt(nn.Module):
                                   d_dtype=d_dtype, p_post=s.p, seed_post=s.seed, relu_input=True, skip_lengths=s.skip)
         if not need_dx:   # last op of the backward pass: nothing left on the main stream to overlap with, and the side stream
             # still has the previous (large) weight gradient queued -- launch here
-            ops.conv1d_wgrad(dc, s.x, G[f'{s.conv_name}.conv.weight'], G[f'{s.conv_name}.conv.bias'], self.cd, lengths_hint)
+            ops.conv1d_wgrad(dc, s.x, G[f'{s.conv_name}.conv.weight'], G[f'{s.conv_name}.conv.bias'], self.cd, s.wgrad_lengths)
             if self._trace_bwd is not None:
                 self._trace_bwd.append(('conv_ln', s, None, dy.clone(), None))     # no data gradient: the input needs none
             return None
-        self._wgrad(dc, s.x, G[f'{s.conv_name}.conv.weight'], G[f'{s.conv_name}.conv.bias'], lengths_hint)
+        self._wgrad(dc, s.x, G[f'{s.conv_name}.conv.weight'], G[f'{s.conv_name}.conv.bias'], s.wgrad_lengths)
         self._block_done()
         if dx_out is not None:
             if self._trace_bwd is not None:
@@ -1008,7 +999,7 @@ class DaftExprt(nn.Module):
             return ops.conv1d(dc, W[f'T:{s.conv_name}.conv.weight'], None, out=dx_out, accumulate=True, skip_lengths=s.skip)
         dx = ops.conv1d(dc, W[f'T:{s.conv_name}.conv.weight'], None, out_dtype=s.x.dtype, skip_lengths=s.skip,
                         w_frag=W.get(f'FT:{s.conv_name}.conv.weight'),
-                        wide_plan=self._plan_wide(s.skip, dc.shape[1]) if f'FT:{s.conv_name}.conv.weight' in W else None)
+                        wide_plan=s.geo.wide if f'FT:{s.conv_name}.conv.weight' in W else None)
         if self._trace_bwd is not None:
             self._trace_bwd.append(('conv_ln', s, None, dy.clone(), dx.clone()))
         return dx
@@ -1062,16 +1053,14 @@ class DaftExprt(nn.Module):
         dfilms = [v.view(B, nb, 2 * ch) for v, (nb, ch) in zip(torch.split(dfilm_all, sizes), layout)]
         # ---- local prosody predictor, on the weight-gradient stream beside everything up to the phoneme encoder (see `overlap_predictor`)
         d_enc_pp, beside = None, d_dur is not None and self._side_stream is not None and self._predictor_beside()
+        main, side, ev = torch.cuda.current_stream(), self._side_stream if beside else None, self._handoff
         if beside:
-            main, side = torch.cuda.current_stream(), self._side_stream
-            self._pp_ev[2].record(main)                                 # the loss gradients and the zeroed FiLM accumulators are in place
-            side.wait_event(self._pp_ev[2])
-            with torch.cuda.stream(side):
+            with _Beside(side, ev, 'predictor bwd') as fork:           # the loss gradients and the zeroed FiLM accumulators are in place
                 d_enc_pp = self._predictor_bwd(W, S, d_dur, d_energy, d_pitch, dfilms[1], None)
-                self._pp_ev[3].record(side)
+                fork.mark('predictor bwd done')
                 # the speaker classifier's backward needs the loss gradient only as well (its d_emb is consumed by the FiLM head far below)
                 d_emb_side = self._classifier_bwd(S, d_spk, zeros)
-                self._pp_ev[4].record(side)
+                fork.mark('classifier bwd done')
             self._wgrad_keep.append((d_enc_pp, d_emb_side))             # (read by the launch stream: stay allocated until the streams have joined)
         # ---- decoder
         blocks, dec_x = S.dec
@@ -1092,8 +1081,7 @@ class DaftExprt(nn.Module):
         dxp, drin, dr = ops.gu_upsample_bwd(d_dec, g.xp, g.weights, g.means, g.ranges, g.r_pre, GP['w_range'], g.input_lengths,
                                             g.output_lengths)
         gu = 'gaussian_upsampling'
-
-        def gu_param_grads():        # three launches that produce parameter gradients only: nothing downstream waits for them
+        with _Beside(side, ev, 'upsampler grads'):      # three launches that produce parameter gradients only: nothing downstream waits for them
             ops.linear_small_bwd(dr.unsqueeze(2), None, g.rin, GP['w_range'], G[f'{gu}.projection.0.linear_layer.weight'],
                                  G[f'{gu}.projection.0.linear_layer.bias'], need_dx=False)
             ops.scalar_embed_bwd(drin, [g.durations_float], [G[f'{gu}.duration_projection.conv.weight']],
@@ -1102,37 +1090,27 @@ class DaftExprt(nn.Module):
                                  [G[f'{gu}.energy_projection.conv.weight'], G[f'{gu}.pitch_projection.conv.weight']],
                                  [G[f'{gu}.energy_projection.conv.bias'], G[f'{gu}.pitch_projection.conv.bias']])
         if beside:
-            self._pp_ev[5].record(main)
-            side.wait_event(self._pp_ev[5])
-            with torch.cuda.stream(side):
-                gu_param_grads()
             self._wgrad_keep.append((dxp, drin, dr))                    # read on the side stream; dxp is NOT modified below (the sum goes into d_enc_pp)
-        else:
-            gu_param_grads()
         d_enc = dxp
         done('gaussian_upsampling')
         # ---- local prosody predictor
         if beside:
-            main.wait_event(self._pp_ev[3])
+            main.wait_event(ev['predictor bwd done'])
             d_enc = ops.add_(d_enc_pp, dxp)                             # (into the predictor's buffer: the side stream may still be reading dxp)
         elif d_dur is not None:
             self._predictor_bwd(W, S, d_dur, d_energy, d_pitch, dfilms[1], d_enc)
         done('prosody_predictor')
         # ---- phoneme encoder
         d_enc = self._fft_stack_bwd(W, S.enc, d_enc, dfilms[0])
-        if beside:                                                      # a parameter gradient only: side stream
-            self._pp_ev[6].record(main)
-            side.wait_event(self._pp_ev[6])
-            with torch.cuda.stream(side):
-                ops.embed_pos_bwd(S.symbols, d_enc, S.input_lengths, G['phoneme_encoder.symbols_embedding.weight'])
-            self._wgrad_keep.append(d_enc)
-        else:
+        with _Beside(side, ev, 'embedding grad'):                      # a parameter gradient only: side stream
             ops.embed_pos_bwd(S.symbols, d_enc, S.input_lengths, G['phoneme_encoder.symbols_embedding.weight'])
+        if beside:
+            self._wgrad_keep.append(d_enc)
         done('phoneme_encoder')
         # ---- speaker classifier (+ gradient reversal, model.py:27-38)
         pe = S.pe
         if beside:
-            main.wait_event(self._pp_ev[4])
+            main.wait_event(ev['classifier bwd done'])
             d_emb = d_emb_side
         else:
             d_emb = self._classifier_bwd(S, d_spk, zeros)
@@ -1165,9 +1143,9 @@ class DaftExprt(nn.Module):
                              [G[f'{pre}.energy_embedding.conv.bias'], G[f'{pre}.pitch_embedding.conv.bias']],
                              lengths=pe.output_lengths, need_dbase=False)
         dl3 = dx
-        dl2 = self._conv_ln_bwd(W, pe.c3, dl3, lengths_hint=pe.output_lengths)
-        dl1 = self._conv_ln_bwd(W, pe.c2, dl2, lengths_hint=pe.output_lengths)
-        self._conv_ln_bwd(W, pe.c1, dl1, need_dx=False, lengths_hint=pe.output_lengths)
+        dl2 = self._conv_ln_bwd(W, pe.c3, dl3)
+        dl1 = self._conv_ln_bwd(W, pe.c2, dl2)
+        self._conv_ln_bwd(W, pe.c1, dl1, need_dx=False)
         done('prosody_encoder.prenet', last=True)
 
     # ------------------------------------------------------------------ fused training step (no autograd graph)
@@ -1259,14 +1237,13 @@ class DaftExprt(nn.Module):
             raise NotImplementedError
         ops.H.require_gpu(symbols, mel_spec_refs)
         self._site = 0
-        self._plans = {}
-        self._hard = {}
         W = self._weights(need_dgrad=False)
-        self._prep(ref_lengths, mel_spec_refs.shape[2])      # tile plans + attention order of a lengths tensor from one launch (as in _forward)
-        self._prep(input_lengths, symbols.shape[1])
-        _, films, _ = self._prosody_encoder_fwd(W, energy_refs, pitch_refs, mel_spec_refs, speaker_ids, ref_lengths, False, False)
-        enc, _ = self._phoneme_encoder_fwd(W, symbols, films[0], input_lengths, False, False)
-        y, _ = self._predictor_fwd(W, enc, films[1], input_lengths, False, False)
+        g_ref = _Geometry(self, ref_lengths, mel_spec_refs.shape[2])
+        g_in = _Geometry(self, input_lengths, symbols.shape[1])
+        self._geometry = (g_ref, g_in)
+        _, films, _ = self._prosody_encoder_fwd(W, energy_refs, pitch_refs, mel_spec_refs, speaker_ids, g_ref, False, False)
+        enc, _ = self._phoneme_encoder_fwd(W, symbols, films[0], g_in, False, False)
+        y, _ = self._predictor_fwd(W, enc, films[1], g_in, False, False)
         dur, energy, pitch = ops.unstack(y, 3)
         dur, dur_int = self.get_int_durations(dur, hparams, dur_factors.contiguous())
         if pitch_transform == 'add':
@@ -1276,8 +1253,9 @@ class DaftExprt(nn.Module):
             ops.prosody_control(energy, pitch, energy_factors.contiguous(), pitch_factors.contiguous(), dur_int, 1)
         output_lengths = self._last_totals
         T = int(output_lengths.max())   # the one host sync of the synthesis path: sizes the output
-        self._prep(output_lengths, T)
+        g_out = _Geometry(self, output_lengths, T)
+        self._geometry += (g_out,)
         dec_in, weights, _, _ = self._upsample_fwd(enc, dur, dur_int, energy, pitch, input_lengths, output_lengths, T, False)
         assert dec_in.size(1) == T   # model.py:914
-        mel, _ = self._decoder_fwd(W, dec_in, films[2], output_lengths, False, False)
+        mel, _ = self._decoder_fwd(W, dec_in, films[2], g_out, False, False)
         return [dur, dur_int, energy, pitch, input_lengths], [mel, output_lengths], weights
