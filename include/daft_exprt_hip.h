@@ -490,6 +490,43 @@ int dx_mel_spectrogram(const float* wav, long ldw, const int64_t* n_samples, con
                        int64_t* n_frames, int B, int T, int n_fft, int hop, int n_mel, int centered, float min_clip,
                        void* stream);
 
+/* ---- K18: Griffin-Lim preview audio (griffin_lim.py:63-198 as called from generate.py:130-137, 311-314).
+ * n_fft in {256, 1024, 4096} and (dx_griffin_lim / dx_gl_normalise) a multiple of hop: DX_ERR_UNSUPPORTED otherwise.
+ *
+ * dx_gl_tables: twiddle (2 * n_fft floats) = exp(-2 pi i t / n_fft), window (n_fft floats) = SYMMETRIC Hann np.hanning(n_fft)
+ * (griffin_lim.py:144), not the periodic window of dx_mel_tables.  Both computed in double, stored fp32.
+ *
+ * dx_mel_to_linear (replaces griffin_lim.py:63-114 `nnls` / `mel_to_linear`): per frame f < lengths[b],
+ *   linear[:, f] ~ argmin_{x >= 0} 1/2 || A x - m ||^2,  m = input_is_log ? exp(mel[b, :, f]) : mel[b, :, f]
+ * started like the reference at clip(pinv(A) m, 0), then `iters` FISTA steps of size `step` (1 / ||A||_2^2).  A = fb
+ * (n_mel, n_fft/2 + 1) with the non-zero bin range [fb_lo[m], fb_hi[m]) of every filter; pinv_t (n_mel, n_fft/2 + 1) =
+ * pinv(A)^T; bin_m / bin_w (n_fft/2 + 1, 2): the (at most two) filters of every bin and their weights (filter -1,
+ * weight 0 where absent).  mel (B, n_mel, T); linear[b, k, f] at b * ld_lb + k * ld_lk + f * ld_lt, zero for
+ * f >= lengths[b].  n_mel <= 256. */
+int dx_gl_tables(float* twiddle, float* window, int n_fft, void* stream);
+int dx_mel_to_linear(const float* mel, const int64_t* lengths, const float* fb, const int* fb_lo, const int* fb_hi,
+                     const float* pinv_t, const int* bin_m, const float* bin_w, float* linear, long ld_lb, long ld_lk,
+                     long ld_lt, int B, int T, int n_mel, int n_fft, int iters, float step, int input_is_log,
+                     void* stream);
+/* dx_griffin_lim (replaces griffin_lim.py:117-173 as called at 194 on linear_spec[:, :-2]): utterance b uses
+ * F_b = max(lengths[b] - 2, 0) frames of mag (b * ld_mb + k * ld_mk + f * ld_mt, k < n_fft/2 + 1) and has
+ * n_samples[b] = F_b * hop + n_fft samples (the reference's trailing hop of zeros included); frames start at
+ * 0, hop, ..., (F_b - 1) * hop.  `iters` >= 1 iterations of: window, rFFT, keep the phase (R / |R|, 1 where R = 0),
+ * swap in mag, irFFT, window, overlap-add in frame order (deterministic), divide by n_fft / hop / 2.  Start: x0 (B, ldx0)
+ * when given, else standard normal noise hashed on the device from (seed, b, sample).  wav (B, ldw), ldw >= S =
+ * max(T - 2, 0) * hop + n_fft, holds the result (unnormalised), zeros past n_samples[b].  ws: dx_gl_ws_floats(B, T, n_fft)
+ * floats of scratch (NULL allowed when that is 0). */
+long dx_gl_ws_floats(int B, int T, int n_fft);
+int dx_griffin_lim(const float* mag, long ld_mb, long ld_mk, long ld_mt, const int64_t* lengths, const float* x0,
+                   long ldx0, const float* twiddle, const float* window, float* wav, long ldw, int64_t* n_samples,
+                   float* ws, int B, int T, int n_fft, int hop, int iters, uint64_t seed, void* stream);
+/* dx_gl_noise: the start signal dx_griffin_lim draws when x0 is NULL (replaces griffin_lim.py:142, np.random.randn): x (B, ldx),
+ * ldx >= S, standard normal from a counter-based hash of (seed, b, sample) and Box-Muller, zeros past n_samples[b]. */
+int dx_gl_noise(float* x, long ldx, const int64_t* lengths, int B, int T, int n_fft, int hop, uint64_t seed, void* stream);
+/* dx_gl_normalise (griffin_lim.py:196, waveform / max|waveform|) in place over the first n_samples of every row; an utterance
+ * with lengths[b] <= 2 or all zeros gives zeros (the reference divides 0 by 0 there). */
+int dx_gl_normalise(float* wav, long ldw, const int64_t* lengths, int B, int T, int n_fft, int hop, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,9 +2,10 @@
 
 Keeps the hot-path part of the reference driver (`src/daft_exprt/generate.py`): `collate_tensors` (140-239: symbol ids,
 per-symbol duration / energy / pitch control factors, reference `.npz` prosody, sort by symbol count, padding rules),
-`generate_batch_mel_specs` (242-317: one `model.inference` call per batch, crop per item, `.npz` with the same keys)
-and `generate_mel_specs` (320-437: chunking + real-time-factor accounting).  Text phonemisation (MFA g2p), plots and
-Griffin-Lim preview audio are outside the accelerated path: sentences arrive phonemised --
+`generate_batch_mel_specs` (242-317: one `model.inference` call per batch, crop per item, `.npz` with the same keys,
+Griffin-Lim preview `.wav` per item on the GPU, `daft_exprt/griffin_lim.py`) and `generate_mel_specs` (320-437: chunking +
+real-time-factor accounting).  Text phonemisation (MFA g2p) and plots are outside the accelerated path (SURVEY 2, rows
+6/13/15): sentences arrive phonemised --
 a list of words (lists of phone symbols) and boundary symbols, exactly what `prepare_sentences_for_inference` returns.
 """
 import logging
@@ -88,7 +89,10 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         (the caller's list is updated like the reference does, 248-253), one `model.inference` call on the collated
         batch, `<output_dir>/<file_name>.npz` holding `mel_spec` (298), and the return value
         `{file_name: [duration, duration_int, energy, pitch, mel_spec, alignment]}` cropped per item (300).
-        Plots / Griffin-Lim preview audio (303-307) are outside the accelerated path: `use_griffin_lim` only warns. '''
+        With `use_griffin_lim` (303-307, 110-137) the preview audio is made on the device from the decoder's mel before the
+        copy to the host (`griffin_lim.griffin_lim_batch`, 30 iterations, device noise seeded with 0) and written as
+        `<output_dir>/<file_name>.wav`: mono, `hparams.sampling_rate`, 64-bit float, peak 1.  Plots stay outside the
+        accelerated path. '''
     for idx, file_name in enumerate(batch_file_names):
         file_name += f'_spk_{batch_speaker_ids[idx]}'
         file_name += f'_ref_{_ref_name(batch_refs[idx], idx)}'
@@ -107,6 +111,9 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
     inputs = tuple(t.to(gpu, non_blocking=True) for t in col[:-1])
     inference = model.inference if hasattr(model, 'inference') else model.module.inference   # DDP-wrapped callers (270-278)
     encoder_preds, decoder_preds, alignments = inference(inputs, pitch_transform, hparams)
+    if use_griffin_lim:
+        from daft_exprt import griffin_lim
+        wavs, n_samples = griffin_lim.griffin_lim_batch(decoder_preds[0].float().contiguous(), decoder_preds[1], hparams)
     duration, duration_int, energy, pitch, input_lengths = (t.detach().cpu().numpy() for t in encoder_preds)
     mel_spec, output_lengths = (t.detach().cpu().numpy() for t in decoder_preds)
     weights = alignments.detach().cpu().numpy()
@@ -118,7 +125,10 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         predictions[f'{name}'] = [duration[i, :l], duration_int[i, :l], energy[i, :l], pitch[i, :l], mel_spec[i, :, :t],
                                   weights[i, :l, :t]]
     if use_griffin_lim:
-        _logger.warning('Griffin-Lim preview audio / plots are outside the accelerated path; use a vocoder on the saved mel-specs')
+        wavs, n_samples = wavs.cpu().numpy(), n_samples.cpu().numpy()
+        for i, name in enumerate(file_names):
+            griffin_lim.write_wav(os.path.join(output_dir, f'{name}.wav'), hparams.sampling_rate, wavs[i, :int(n_samples[i])])
+        _logger.warning('Mel-spec / alignment plots are outside the accelerated path')
     return predictions
 
 
