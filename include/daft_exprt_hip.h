@@ -527,6 +527,30 @@ int dx_gl_noise(float* x, long ldx, const int64_t* lengths, int B, int T, int n_
  * with lengths[b] <= 2 or all zeros gives zeros (the reference divides 0 by 0 there). */
 int dx_gl_normalise(float* wav, long ldw, const int64_t* lengths, int B, int T, int n_fft, int hop, void* stream);
 
+/* ---- K19: audio of the vocoder fine-tuning data set (fine_tune.py:91-115).
+ *
+ * dx_resample (replaces fine_tune.py:92, `librosa.load(wav_file, sr=hparams.sampling_rate)` when the file's rate differs:
+ * librosa 0.8.1 `resample(res_type='kaiser_best')` -> resampy): x (B, ldx) fp32 with n_in[b] <= S_in samples per row ->
+ * y (B, ldy), S_out = ceil(S_in * sr_out / sr_in) <= ldy, n_out[b] = ceil(n_in[b] * sr_out / sr_in) (librosa's length; may be
+ * NULL).  With g = gcd(sr_in, sr_out), P = sr_out / g, Q = sr_in / g, output t < floor(n_in[b] * P / Q) is
+ *     y[b, t] = sum_{j < taps} bank[j * P + t mod P] * x[b, floor(t Q / P) - (left - 1) + j]     (x = 0 outside [0, n_in[b]))
+ * summed in fp32 in tap order; outputs from floor(n_in[b] * P / Q) on are 0 (librosa's fix_length pads the ceiling sample).
+ * bank: (taps, P) fp32, tap-major, built on the host (daft_exprt/audio.py `resample_bank`) from the windowed-sinc table;
+ * `left` taps sit at or before floor(t Q / P).  Equal rates copy x (bank may be NULL), as librosa skips resampling.
+ * P * taps > dx_resample_max_weights() or a ratio whose 512-output run stages more than 16384 input samples:
+ * DX_ERR_UNSUPPORTED (every rate pair among 8, 16, 22.05, 24, 32, 44.1 and 48 kHz fits). */
+long dx_resample_max_weights(void);
+int dx_resample(const float* x, long ldx, const int64_t* n_in, const float* bank, float* y, long ldy, int64_t* n_out,
+                int B, long S_in, long S_out, int sr_in, int sr_out, int taps, int left, void* stream);
+/* dx_ft_pack (replaces fine_tune.py:75-109: mel_spec_preds.cpu(), mel_spec_pred[:, :output_length], wav[begin:end],
+ * (wav * 32768.0).astype('int16')): mel (b * ld_mb + m * ld_mk + f) fp32 (B, n_mel, T) -> mel_out, utterance b as a
+ * contiguous (n_mel, T_b) block, T_b = min(lengths[b], T), blocks back to back in batch order (offset n_mel * sum_{i<b} T_i).
+ * wav (B, ldw) fp32, crop (B, 2) int64 = (begin_b, len_b) with 0 <= begin_b, begin_b + len_b <= S -> wav_out int16, utterance b
+ * at offset sum_{i<b} len_i: trunc(wav[b, begin_b + s] * 32768) for s < len_b.  Values outside the int16 range saturate to
+ * -32768 / 32767 and NaN gives 0 (the reference's cast is undefined there); samples outside [0, S) are written as 0. */
+int dx_ft_pack(const float* mel, long ld_mb, long ld_mk, const int64_t* lengths, int B, int n_mel, int T, const float* wav,
+               long ldw, const int64_t* crop, long S, float* mel_out, int16_t* wav_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

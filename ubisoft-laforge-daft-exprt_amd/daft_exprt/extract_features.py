@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from daft_exprt import _hip as H
+from daft_exprt.audio import rescale_wav_to_float32  # noqa: F401  (the reference keeps it here, `extract_features.py:362`)
 
 _TABLES = {}
 
