@@ -1,7 +1,7 @@
 """Mel / energy front-end.  CPU: the oracle restatement against the fixture produced by the reference's
 own `mel_spectrogram_HiFi` (tools/gen_golden_mel_frontend.py); GPU: the HIP kernels against the same fixture.
 Tolerances: oracle vs fixture 1e-5 (same torch.stft); GPU vs fixture 2e-3 absolute on the log-mel values above the
-clamp floor region (DFT as an fp32 GEMM vs torch's FFT: both fp32, different summation order; log amplifies relative
+clamp floor region (radix-4 FFT in LDS vs torch's FFT: both fp32, different summation order; log amplifies relative
 error of near-silent bins) and 1e-3 relative on the frame energies."""
 import os
 

@@ -11,23 +11,9 @@
 //                   complex radix-4 Stockham FFT in LDS, forward and inverse), then a gather overlap-add in frame order
 //                   (no atomics: bit-reproducible) divided by n_fft / hop / 2.  Two launches per iteration.
 //   normalise:      x / max|x| per utterance; an utterance with no frame or all zeros gives zeros (the reference: 0 / 0).
-#include "dx_common.h"
+#include "dx_fft.h"
 
 namespace {
-
-struct cplx { float re, im; };
-__device__ __forceinline__ cplx cmul(cplx a, cplx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-
-// twiddle[t] = exp(-2 pi i t / n_fft); window[n] = SYMMETRIC Hann (np.hanning): 0.5 - 0.5 cos(2 pi n / (n_fft - 1))
-__global__ void gl_tables_kernel(float* __restrict__ twiddle, float* __restrict__ window, int n_fft) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= n_fft) return;
-  double s, c;
-  sincospi(2.0 * (double)n / (double)n_fft, &s, &c);
-  twiddle[2 * n] = (float)c;
-  twiddle[2 * n + 1] = (float)(-s);
-  window[n] = (float)(0.5 - 0.5 * cospi(2.0 * (double)n / (double)(n_fft - 1)));
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // mel -> linear magnitude (NNLS)
@@ -138,41 +124,6 @@ __global__ __launch_bounds__(64) void gl_nnls_kernel(NnlsArgs a) {
 
 __device__ __forceinline__ int gl_nframes(int64_t len) { return len > 2 ? (int)(len - 2) : 0; }   // spec[:, :-2]
 
-// In-LDS radix-4 Stockham FFT of NFFT complex points (forward, exp(-2 pi i k n / N)), NFFT / 4 threads, one butterfly per
-// thread per stage; input in buffer `cur`, returns the buffer holding the output.  Same stage loop as frontend.hip.
-template <int NFFT>
-__device__ __forceinline__ int gl_fft(float (*bufr)[NFFT], float (*bufi)[NFFT], int cur, const float* __restrict__ twiddle, int j) {
-  constexpr int NT = NFFT / 4;
-#pragma unroll
-  for (int Ns = 1; Ns < NFFT; Ns *= 4) {
-    const int k = j & (Ns - 1);
-    cplx v[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = {bufr[cur][j + r * NT], bufi[cur][j + r * NT]};
-    if (Ns > 1) {
-      const int t = k * (NFFT / (4 * Ns));
-#pragma unroll
-      for (int r = 1; r < 4; ++r) {
-        const cplx w = {twiddle[2 * (r * t)], twiddle[2 * (r * t) + 1]};
-        v[r] = cmul(v[r], w);
-      }
-    }
-    const cplx s02 = {v[0].re + v[2].re, v[0].im + v[2].im}, d02 = {v[0].re - v[2].re, v[0].im - v[2].im};
-    const cplx s13 = {v[1].re + v[3].re, v[1].im + v[3].im}, d13 = {v[1].re - v[3].re, v[1].im - v[3].im};
-    const cplx y0 = {s02.re + s13.re, s02.im + s13.im}, y2 = {s02.re - s13.re, s02.im - s13.im};
-    const cplx y1 = {d02.re + d13.im, d02.im - d13.re};
-    const cplx y3 = {d02.re - d13.im, d02.im + d13.re};
-    const int o = (j - k) * 4 + k;
-    bufr[cur ^ 1][o] = y0.re; bufi[cur ^ 1][o] = y0.im;
-    bufr[cur ^ 1][o + Ns] = y1.re; bufi[cur ^ 1][o + Ns] = y1.im;
-    bufr[cur ^ 1][o + 2 * Ns] = y2.re; bufi[cur ^ 1][o + 2 * Ns] = y2.im;
-    bufr[cur ^ 1][o + 3 * Ns] = y3.re; bufi[cur ^ 1][o + 3 * Ns] = y3.im;
-    cur ^= 1;
-    __syncthreads();
-  }
-  return cur;
-}
-
 // S * R / |R|, R = 0 -> S (np.angle(0) = 0)
 __device__ __forceinline__ cplx gl_swap_mag(float re, float im, float s) {
   const float m = hypotf(re, im);
@@ -203,7 +154,7 @@ __global__ __launch_bounds__(NFFT / 4) void gl_frames_kernel(FrameArgs a) {
     bufi[0][n] = has1 ? w * x[n + a.hop] : 0.f;
   }
   __syncthreads();
-  int cur = gl_fft<NFFT>(bufr, bufi, 0, a.twiddle, j);
+  int cur = dx_fft_lds<NFFT>(bufr, bufi, 0, a.twiddle, j);
   const float* S = a.mag + (long)b * a.ld_mb + (long)f0 * a.ld_mt;
   cplx y1v[(H + NT) / NT], y2v[(H + NT) / NT];
 #pragma unroll
@@ -232,7 +183,7 @@ __global__ __launch_bounds__(NFFT / 4) void gl_frames_kernel(FrameArgs a) {
     }
   }
   __syncthreads();
-  cur = gl_fft<NFFT>(bufr, bufi, nxt, a.twiddle, j);              // ifft(Z) = conj(fft(conj Z)) / N
+  cur = dx_fft_lds<NFFT>(bufr, bufi, nxt, a.twiddle, j);          // ifft(Z) = conj(fft(conj Z)) / N
   constexpr float inv_n = 1.f / NFFT;
   float* o0 = a.frames + ((long)b * a.Fcap + f0) * NFFT;
 #pragma unroll
@@ -302,14 +253,24 @@ __global__ __launch_bounds__(256) void gl_normalise_kernel(float* __restrict__ x
   for (long s = j; s < S; s += 256) xb[s] = (zero || s >= Sb) ? 0.f : xb[s] / m;
 }
 
-bool gl_nfft_ok(int n_fft) { return n_fft == 256 || n_fft == 1024 || n_fft == 4096; }
+// What dx_griffin_lim, dx_gl_noise and dx_gl_normalise require of their shape: a T-frame batch makes S = max(T - 2, 0) * hop +
+// n_fft samples per utterance, and the rows (`ld` floats apart) must hold them.  `fn`: the entry point, for the message.
+int gl_check_shape(const char* fn, int B, int T, int n_fft, int hop, long ld, long* S) {
+  DX_REQUIRE(B > 0 && T > 0 && hop > 0, DX_ERR_SHAPE, "%s: bad shape B=%d T=%d hop=%d", fn, B, T, hop);
+  DX_REQUIRE(dx_nfft_ok(n_fft) && n_fft % hop == 0, DX_ERR_UNSUPPORTED,
+             "%s: n_fft=%d hop=%d unsupported (n_fft 256, 1024 or 4096, a multiple of hop)", fn, n_fft, hop);
+  *S = (long)(T > 2 ? T - 2 : 0) * hop + n_fft;
+  DX_REQUIRE(ld >= *S, DX_ERR_SHAPE, "%s: rows hold %ld < %ld samples", fn, ld, *S);
+  return DX_OK;
+}
 
 }  // namespace
 
 extern "C" int dx_gl_tables(float* twiddle, float* window, int n_fft, void* stream) {
   DX_REQUIRE(twiddle && window, DX_ERR_ARG, "dx_gl_tables: null pointer");
-  DX_REQUIRE(gl_nfft_ok(n_fft), DX_ERR_UNSUPPORTED, "dx_gl_tables: n_fft=%d unsupported (256, 1024 or 4096)", n_fft);
-  hipLaunchKernelGGL(gl_tables_kernel, dim3(dx_cdiv(n_fft, 256)), dim3(256), 0, (hipStream_t)stream, twiddle, window, n_fft);
+  DX_REQUIRE(dx_nfft_ok(n_fft), DX_ERR_UNSUPPORTED, "dx_gl_tables: n_fft=%d unsupported (256, 1024 or 4096)", n_fft);
+  hipLaunchKernelGGL(dx_fft_tables_kernel<DX_HANN_SYMMETRIC>, dim3(dx_cdiv(n_fft, 256)), dim3(256), 0, (hipStream_t)stream, twiddle,
+                     window, n_fft);
   DX_LAUNCH_CHECK();
   return DX_OK;
 }
@@ -323,13 +284,11 @@ extern "C" int dx_mel_to_linear(const float* mel, const int64_t* lengths, const 
   DX_REQUIRE(B > 0 && T > 0 && n_mel > 0 && n_mel <= NNLS_MAX_MEL && iters >= 0 && step > 0.f, DX_ERR_SHAPE,
              "dx_mel_to_linear: bad shape B=%d T=%d n_mel=%d (<= %d) iters=%d step=%g", B, T, n_mel, NNLS_MAX_MEL, iters,
              (double)step);
-  DX_REQUIRE(gl_nfft_ok(n_fft), DX_ERR_UNSUPPORTED, "dx_mel_to_linear: n_fft=%d unsupported (256, 1024 or 4096)", n_fft);
   NnlsArgs a{mel, lengths, fb, fb_lo, fb_hi, pinv_t, bin_m, bin_w, linear, ld_lb, ld_lk, ld_lt, T, n_mel, iters, input_is_log, step};
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(T, B);
-  if (n_fft == 1024) hipLaunchKernelGGL(gl_nnls_kernel<1024>, grid, dim3(64), 0, s, a);
-  else if (n_fft == 256) hipLaunchKernelGGL(gl_nnls_kernel<256>, grid, dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(gl_nnls_kernel<4096>, grid, dim3(64), 0, s, a);
+  const bool ok = dx_nfft_dispatch(n_fft, [&](auto N) {
+    hipLaunchKernelGGL(gl_nnls_kernel<decltype(N)::value>, dim3(T, B), dim3(64), 0, (hipStream_t)stream, a);
+  });
+  DX_REQUIRE(ok, DX_ERR_UNSUPPORTED, "dx_mel_to_linear: n_fft=%d unsupported (256, 1024 or 4096)", n_fft);
   DX_LAUNCH_CHECK();
   return DX_OK;
 }
@@ -342,14 +301,10 @@ extern "C" int dx_griffin_lim(const float* mag, long ld_mb, long ld_mk, long ld_
                               long ldx0, const float* twiddle, const float* window, float* wav, long ldw, int64_t* n_samples,
                               float* ws, int B, int T, int n_fft, int hop, int iters, uint64_t seed, void* stream) {
   DX_REQUIRE(mag && lengths && twiddle && window && wav && n_samples && (ws || T <= 2), DX_ERR_ARG, "dx_griffin_lim: null pointer");
-  DX_REQUIRE(B > 0 && T > 0 && hop > 0 && iters >= 1, DX_ERR_SHAPE, "dx_griffin_lim: bad shape B=%d T=%d hop=%d iters=%d",
-             B, T, hop, iters);
-  DX_REQUIRE(gl_nfft_ok(n_fft) && n_fft % hop == 0, DX_ERR_UNSUPPORTED,
-             "dx_griffin_lim: n_fft=%d hop=%d unsupported (n_fft 256, 1024 or 4096, a multiple of hop)", n_fft, hop);
+  DX_REQUIRE(iters >= 1, DX_ERR_SHAPE, "dx_griffin_lim: bad shape iters=%d", iters);
+  long S;
+  if (const int rc = gl_check_shape("dx_griffin_lim", B, T, n_fft, hop, x0 && ldx0 < ldw ? ldx0 : ldw, &S)) return rc;
   const int Fcap = T > 2 ? T - 2 : 0;
-  const long S = (long)Fcap * hop + n_fft;
-  DX_REQUIRE(ldw >= S && (!x0 || ldx0 >= S), DX_ERR_SHAPE, "dx_griffin_lim: rows of wav / x0 hold %ld / %ld < %ld samples",
-             ldw, ldx0, S);
   hipStream_t s = (hipStream_t)stream;
   const dim3 sgrid((unsigned)((S + 255) / 256), B);
   const float scale = (float)((double)n_fft / hop / 2.0);
@@ -362,10 +317,10 @@ extern "C" int dx_griffin_lim(const float* mag, long ld_mb, long ld_mk, long ld_
   for (int it = 0; it < iters; ++it) {
     if (Fcap > 0) {
       FrameArgs a{src, lds, mag, ld_mb, ld_mk, ld_mt, lengths, twiddle, window, ws, Fcap, hop};
-      dim3 grid(dx_cdiv(Fcap, 2), B);
-      if (n_fft == 1024) hipLaunchKernelGGL(gl_frames_kernel<1024>, grid, dim3(256), 0, s, a);
-      else if (n_fft == 256) hipLaunchKernelGGL(gl_frames_kernel<256>, grid, dim3(64), 0, s, a);
-      else hipLaunchKernelGGL(gl_frames_kernel<4096>, grid, dim3(1024), 0, s, a);
+      dx_nfft_dispatch(n_fft, [&](auto N) {
+        constexpr int NFFT = decltype(N)::value;
+        hipLaunchKernelGGL(gl_frames_kernel<NFFT>, dim3(dx_cdiv(Fcap, 2), B), dim3(NFFT / 4), 0, s, a);
+      });
       DX_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(gl_ola_kernel, sgrid, dim3(256), 0, s, ws, lengths, wav, ldw, n_samples, S, Fcap, n_fft, hop, scale);
@@ -379,11 +334,8 @@ extern "C" int dx_griffin_lim(const float* mag, long ld_mb, long ld_mk, long ld_
 extern "C" int dx_gl_noise(float* x, long ldx, const int64_t* lengths, int B, int T, int n_fft, int hop, uint64_t seed,
                            void* stream) {
   DX_REQUIRE(x && lengths, DX_ERR_ARG, "dx_gl_noise: null pointer");
-  DX_REQUIRE(B > 0 && T > 0 && hop > 0, DX_ERR_SHAPE, "dx_gl_noise: bad shape B=%d T=%d hop=%d", B, T, hop);
-  DX_REQUIRE(gl_nfft_ok(n_fft) && n_fft % hop == 0, DX_ERR_UNSUPPORTED,
-             "dx_gl_noise: n_fft=%d hop=%d unsupported (n_fft 256, 1024 or 4096, a multiple of hop)", n_fft, hop);
-  const long S = (long)(T > 2 ? T - 2 : 0) * hop + n_fft;
-  DX_REQUIRE(ldx >= S, DX_ERR_SHAPE, "dx_gl_noise: rows of x hold %ld < %ld samples", ldx, S);
+  long S;
+  if (const int rc = gl_check_shape("dx_gl_noise", B, T, n_fft, hop, ldx, &S)) return rc;
   hipLaunchKernelGGL(gl_noise_kernel, dim3((unsigned)((S + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, x, ldx, lengths,
                      S, n_fft, hop, seed);
   DX_LAUNCH_CHECK();
@@ -392,11 +344,8 @@ extern "C" int dx_gl_noise(float* x, long ldx, const int64_t* lengths, int B, in
 
 extern "C" int dx_gl_normalise(float* wav, long ldw, const int64_t* lengths, int B, int T, int n_fft, int hop, void* stream) {
   DX_REQUIRE(wav && lengths, DX_ERR_ARG, "dx_gl_normalise: null pointer");
-  DX_REQUIRE(B > 0 && T > 0 && hop > 0, DX_ERR_SHAPE, "dx_gl_normalise: bad shape B=%d T=%d hop=%d", B, T, hop);
-  DX_REQUIRE(gl_nfft_ok(n_fft) && n_fft % hop == 0, DX_ERR_UNSUPPORTED,
-             "dx_gl_normalise: n_fft=%d hop=%d unsupported (n_fft 256, 1024 or 4096, a multiple of hop)", n_fft, hop);
-  const long S = (long)(T > 2 ? T - 2 : 0) * hop + n_fft;
-  DX_REQUIRE(ldw >= S, DX_ERR_SHAPE, "dx_gl_normalise: rows of wav hold %ld < %ld samples", ldw, S);
+  long S;
+  if (const int rc = gl_check_shape("dx_gl_normalise", B, T, n_fft, hop, ldw, &S)) return rc;
   hipLaunchKernelGGL(gl_normalise_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, wav, ldw, lengths, S, n_fft, hop);
   DX_LAUNCH_CHECK();
   return DX_OK;

@@ -98,3 +98,19 @@ def require_gpu(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
             raise RuntimeError('daft_exprt HIP kernels need device tensors (no CPU fallback)')
+
+
+def device(device=None):
+    ''' the device of the NumPy-in / NumPy-out entry points: `device`, or cuda:0 '''
+    return torch.device(device if device is not None else 'cuda:0')
+
+
+_DEVICE_TABLES = {}     # (kind, device, ...) -> constant device-resident tables, each built once per process
+
+
+def device_table(kind, device, *params, make=None):
+    ''' the table of this kind and these parameters on `device`; `make()` builds it the first time it is asked for '''
+    key = (kind, str(device)) + params
+    if key not in _DEVICE_TABLES:
+        _DEVICE_TABLES[key] = make()
+    return _DEVICE_TABLES[key]

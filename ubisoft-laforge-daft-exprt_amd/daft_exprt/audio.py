@@ -28,8 +28,6 @@ PRECISION = 9
 ROLLOFF = 0.9475937167399596
 KAISER_BETA = 14.769656459379492
 
-_BANKS = {}
-
 
 @functools.lru_cache(maxsize=1)
 def filter_table():
@@ -88,11 +86,26 @@ def resample_bank(sr_in, sr_out):
 
 
 def _device_bank(sr_in, sr_out, device):
-    key = (str(device), int(sr_in), int(sr_out))
-    if key not in _BANKS:
+    def make():
         bank, left = resample_bank(sr_in, sr_out)
-        _BANKS[key] = (torch.from_numpy(bank.astype(np.float32)).to(device), left)
-    return _BANKS[key]
+        return torch.from_numpy(bank.astype(np.float32)).to(device), left
+    return H.device_table('resample', device, int(sr_in), int(sr_out), make=make)
+
+
+def fft_tables(n_fft, symmetric, device):
+    ''' (twiddle (2 n_fft,) fp32: exp(-2 pi i t / n_fft) as (cos, sin) pairs, Hann window (n_fft,) fp32) of the in-LDS FFT on
+        `device`: the periodic window of `torch.hann_window` (the STFT of the mel front-end) or, with `symmetric`, `np.hanning`
+        (Griffin-Lim).  The table entry points write both; the twiddles do not depend on the window, so those of the first
+        call are kept for both kinds. '''
+    def make_window():
+        twiddle = torch.empty(2 * n_fft, dtype=torch.float32, device=device)
+        window = torch.empty(n_fft, dtype=torch.float32, device=device)
+        tables = H.lib().dx_gl_tables if symmetric else H.lib().dx_mel_tables
+        H.check(tables(H.ptr(twiddle), H.ptr(window), n_fft, H.stream()))
+        H.device_table('twiddle', device, n_fft, make=lambda: twiddle)
+        return window
+    window = H.device_table('window', device, n_fft, bool(symmetric), make=make_window)
+    return H.device_table('twiddle', device, n_fft), window
 
 
 def resample_batch(wavs, n_in, sr_in, sr_out):
@@ -188,7 +201,7 @@ def load_wav(path, sr=22050, device=None):
     y = to_float_mono(y)
     if sr is None or int(sr) == rate:
         return y, rate
-    dev = torch.device(device if device is not None else 'cuda:0')
+    dev = H.device(device)
     x = torch.from_numpy(y).reshape(1, -1).to(dev)
     n = torch.tensor([y.shape[0]], dtype=torch.int64, device=dev)
     out, _ = resample_batch(x, n, rate, int(sr))
@@ -211,12 +224,18 @@ def rescale_wav_to_float32(x):
     return y.astype('float32')
 
 
+def _wav_header(tag, sampling_rate, sample_bytes, n_samples, fmt_tail=b'', chunks=b''):
+    ''' RIFF / WAVE header of n_samples mono samples of sample_bytes each: the `fmt ` chunk (format `tag`, closed by
+        `fmt_tail`), `chunks` as they stand, and the header of the `data` chunk, whose samples the caller appends '''
+    rate, nbytes = int(sampling_rate), sample_bytes * int(n_samples)
+    fmt = struct.pack('<HHIIHH', tag, 1, rate, rate * sample_bytes, sample_bytes, 8 * sample_bytes) + fmt_tail
+    body = b'WAVE' + b'fmt ' + struct.pack('<I', len(fmt)) + fmt + chunks + b'data' + struct.pack('<I', nbytes)
+    return b'RIFF' + struct.pack('<I', len(body) + nbytes) + body
+
+
 def wav_int16_header(sampling_rate, n_samples):
     ''' the 44-byte header `scipy.io.wavfile.write` puts in front of n_samples int16 mono samples '''
-    nbytes = 2 * int(n_samples)
-    fmt = struct.pack('<HHIIHH', 1, 1, int(sampling_rate), 2 * int(sampling_rate), 2, 16)
-    return b'RIFF' + struct.pack('<I', 36 + nbytes) + b'WAVE' + b'fmt ' + struct.pack('<I', 16) + fmt + b'data' + \
-        struct.pack('<I', nbytes)
+    return _wav_header(1, sampling_rate, 2, n_samples)
 
 
 def write_wav_int16(path, sampling_rate, data):
@@ -226,3 +245,13 @@ def write_wav_int16(path, sampling_rate, data):
     with open(path, 'wb') as f:
         f.write(wav_int16_header(sampling_rate, data.size))
         f.write(data.astype('<i2', copy=False).tobytes())
+
+
+def write_wav(path, sampling_rate, data):
+    ''' mono 64-bit IEEE-float WAV -- what `scipy.io.wavfile.write` makes of the reference's float64 waveform
+        (generate.py:137): RIFF / WAVE, `fmt ` (format 3, 18 bytes: cbSize = 0), `fact` (the sample count), `data` '''
+    data = np.ascontiguousarray(np.asarray(data, dtype='<f8').reshape(-1))
+    fact = b'fact' + struct.pack('<II', 4, data.size)
+    with open(path, 'wb') as f:
+        f.write(_wav_header(3, sampling_rate, 8, data.size, fmt_tail=struct.pack('<H', 0), chunks=fact))
+        f.write(data.tobytes())

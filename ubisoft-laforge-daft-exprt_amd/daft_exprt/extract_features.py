@@ -11,9 +11,8 @@ import numpy as np
 import torch
 
 from daft_exprt import _hip as H
+from daft_exprt.audio import fft_tables
 from daft_exprt.audio import rescale_wav_to_float32  # noqa: F401  (the reference keeps it here, `extract_features.py:362`)
-
-_TABLES = {}
 
 
 def _hz_to_mel(f):
@@ -42,19 +41,16 @@ def mel_filter_bank(sr, n_fft, n_mels, fmin, fmax):
     return fb.astype(np.float32)
 
 
-def _tables(hparams, device):
-    key = (str(device), hparams.sampling_rate, hparams.filter_length, hparams.n_mel_channels, hparams.mel_fmin, hparams.mel_fmax)
-    if key not in _TABLES:
-        n_fft = int(hparams.filter_length)
-        basis = torch.empty(2 * n_fft, dtype=torch.float32, device=device)      # FFT twiddles exp(-2 pi i t / n_fft)
-        window = torch.empty(n_fft, dtype=torch.float32, device=device)
-        H.check(H.lib().dx_mel_tables(H.ptr(basis), H.ptr(window), n_fft, H.stream()))
-        fb = mel_filter_bank(hparams.sampling_rate, n_fft, hparams.n_mel_channels, hparams.mel_fmin, hparams.mel_fmax)
+def mel_tables(hparams, device):
+    ''' (filterbank (n_mel, n_fft/2 + 1) fp32, lo, hi (n_mel,) int32: filter m is non-zero on bins lo[m] .. hi[m] - 1) on `device` '''
+    def make():
+        fb = mel_filter_bank(hparams.sampling_rate, int(hparams.filter_length), hparams.n_mel_channels, hparams.mel_fmin, hparams.mel_fmax)
         nz = fb > 0
         lo = np.where(nz.any(1), nz.argmax(1), 0).astype(np.int32)
         hi = np.where(nz.any(1), fb.shape[1] - nz[:, ::-1].argmax(1), 0).astype(np.int32)
-        _TABLES[key] = (basis, window, torch.from_numpy(fb).to(device), torch.from_numpy(lo).to(device), torch.from_numpy(hi).to(device))
-    return _TABLES[key]
+        return torch.from_numpy(fb).to(device), torch.from_numpy(lo).to(device), torch.from_numpy(hi).to(device)
+    return H.device_table('mel', device, hparams.sampling_rate, hparams.filter_length, hparams.n_mel_channels, hparams.mel_fmin,
+                          hparams.mel_fmax, make=make)
 
 
 def nb_frames(n_samples, hparams):
@@ -76,7 +72,8 @@ def mel_spectrogram_batch(wavs, n_samples, hparams):
     if hparams.centered and int(n_samples.min()) <= n_fft // 2:
         raise ValueError('mel_spectrogram: reflect padding needs more than filter_length / 2 samples')
     T = max(1, nb_frames(S, hparams))
-    basis, window, fb, lo, hi = _tables(hparams, dev)
+    basis, window = fft_tables(n_fft, False, dev)
+    fb, lo, hi = mel_tables(hparams, dev)
     mel = torch.empty((B, n_mel, T), dtype=torch.float32, device=dev)
     energy = torch.empty((B, T), dtype=torch.float32, device=dev)
     n_frames = torch.empty((B,), dtype=torch.int64, device=dev)

@@ -14,39 +14,24 @@ Where this differs from the reference, by design:
     from a given signal.
   * an utterance of at most 2 frames, or an all-zero signal, normalises to zeros (the reference computes 0 / 0 = NaN).
 """
-import struct
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from daft_exprt import _hip as H
-from daft_exprt import extract_features as FE
+from daft_exprt.audio import fft_tables, write_wav  # noqa: F401  (write_wav: the preview audio's writer, kept importable here)
+from daft_exprt.extract_features import mel_tables
 
 NNLS_ITERS = 500        # FISTA steps after the clipped-pinv start: on tests/golden/griffin_lim.npz the per-frame residual
                         # is within the reference's on every frame from ~400 on in fp32 (200: 4 % of the decoder frames)
 GL_ITERS = 30           # griffin_lim.py:194
 
-_TABLES = {}
 
-
-def _gl_tables(n_fft, device):
-    ''' (twiddle, symmetric Hann window) of the Griffin-Lim FFT '''
-    key = ('gl', str(device), int(n_fft))
-    if key not in _TABLES:
-        twiddle = torch.empty(2 * n_fft, dtype=torch.float32, device=device)
-        window = torch.empty(n_fft, dtype=torch.float32, device=device)
-        H.check(H.lib().dx_gl_tables(H.ptr(twiddle), H.ptr(window), int(n_fft), H.stream()))
-        _TABLES[key] = (twiddle, window)
-    return _TABLES[key]
-
-
-def _tables(hparams, device):
-    ''' (fb, lo, hi, pinv(A)^T, bin_m, bin_w, step) of the mel -> linear solve for these hparams on `device` '''
-    key = (str(device), hparams.sampling_rate, hparams.filter_length, hparams.n_mel_channels, hparams.mel_fmin, hparams.mel_fmax)
-    if key not in _TABLES:
-        _, _, fb, lo, hi = FE._tables(hparams, device)
-        A = fb.cpu().numpy().astype(np.float64)
+def _nnls_tables(hparams, device):
+    ''' (pinv(A)^T, bin_m, bin_w, step) of the mel -> linear solve for these hparams on `device`; A = the mel filterbank '''
+    def make():
+        A = mel_tables(hparams, device)[0].cpu().numpy().astype(np.float64)
         pinv_t = np.ascontiguousarray(np.linalg.pinv(A).T).astype(np.float32)       # (n_mel, n_fft/2 + 1)
         step = 1.0 / np.linalg.norm(A, 2) ** 2
         nb = A.shape[1]
@@ -59,8 +44,9 @@ def _tables(hparams, device):
             bin_m[k, :len(ms)] = ms
             bin_w[k, :len(ms)] = A[ms, k]
         to = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
-        _TABLES[key] = (fb, lo, hi, to(pinv_t), to(bin_m), to(bin_w), float(step))
-    return _TABLES[key]
+        return to(pinv_t), to(bin_m), to(bin_w), float(step)
+    return H.device_table('nnls', device, hparams.sampling_rate, hparams.filter_length, hparams.n_mel_channels, hparams.mel_fmin,
+                          hparams.mel_fmax, make=make)
 
 
 def n_samples(T, hparams):
@@ -79,7 +65,8 @@ def mel_to_linear_batch(mel, lengths, hparams, nnls_iters=None, input_is_log=Tru
     B, n_mel, T = mel.shape
     n_fft = int(hparams.filter_length)
     nb = n_fft // 2 + 1
-    fb, lo, hi, pinv_t, bin_m, bin_w, step = _tables(hparams, mel.device)
+    fb, lo, hi = mel_tables(hparams, mel.device)
+    pinv_t, bin_m, bin_w, step = _nnls_tables(hparams, mel.device)
     lin = torch.empty((B, T, nb), dtype=torch.float32, device=mel.device)
     iters = NNLS_ITERS if nnls_iters is None else int(nnls_iters)
     H.check(H.lib().dx_mel_to_linear(H.ptr(mel), H.ptr(lengths), H.ptr(fb), H.ptr(lo), H.ptr(hi), H.ptr(pinv_t), H.ptr(bin_m),
@@ -99,7 +86,7 @@ def griffin_lim_from_linear(linear, lengths, hparams, iterations=GL_ITERS, seed=
     n_fft, hop = int(hparams.filter_length), int(hparams.hop_length)
     assert nb == n_fft // 2 + 1, (nb, n_fft)
     dev = linear.device
-    twiddle, window = _gl_tables(n_fft, dev)
+    twiddle, window = fft_tables(n_fft, True, dev)
     S = n_samples(T, hparams)
     if x0 is not None:
         assert x0.dtype == torch.float32 and x0.dim() == 2 and x0.shape[0] == B and x0.shape[1] >= S and x0.stride(1) == 1
@@ -126,13 +113,9 @@ def griffin_lim_batch(mel, lengths, hparams, iterations=GL_ITERS, seed=0, x0=Non
 
 # ---- reference signatures (NumPy in / out, one utterance) -------------------------------------------------------------
 
-def _device(device):
-    return torch.device(device if device is not None else 'cuda:0')
-
-
 def mel_to_linear(mel_spectrogram, hparams, device=None):
     ''' `griffin_lim.py:102-114`: LINEAR mel (n_mels, T) -> linear magnitude (n_fft // 2 + 1, T) float32 '''
-    dev = _device(device)
+    dev = H.device(device)
     mel = torch.as_tensor(np.asarray(mel_spectrogram, dtype=np.float32))
     n_mel, T = mel.shape
     lengths = torch.tensor([T], dtype=torch.int64, device=dev)
@@ -145,7 +128,7 @@ def reconstruct_signal_griffin_lim(magnitude_spectrogram, step_size, iterations,
         spectrogram (F, n_fft // 2 + 1) complex128).  The start is `x0` if given, else device noise from `seed` (the
         reference draws unseeded np.random.randn).  The proposal -- dropped by every caller of the reference -- is formed
         on the host from the signal before the last iteration. '''
-    dev = _device(device)
+    dev = H.device(device)
     mag = np.asarray(magnitude_spectrogram, dtype=np.float32)
     nb, F = mag.shape
     n_fft, hop = (nb - 1) * 2, int(step_size)
@@ -172,7 +155,7 @@ def reconstruct_signal_griffin_lim(magnitude_spectrogram, step_size, iterations,
 def griffin_lim_reconstruction_from_mel_spec(mel_spec, hparams, logger, seed=0, device=None):
     ''' `griffin_lim.py:176-198`: log-mel (n_mels, T) -> normalised waveform (max(T - 2, 0) * hop + n_fft,) float64
         (zeros for T <= 2, where the reference divides 0 by 0) '''
-    dev = _device(device)
+    dev = H.device(device)
     mel = torch.as_tensor(np.asarray(mel_spec, dtype=np.float32))
     n_mel, T = mel.shape
     lengths = torch.tensor([T], dtype=torch.int64, device=dev)
@@ -191,18 +174,3 @@ def device_noise(lengths, hparams, T, seed=0):
     x = torch.empty((B, S), dtype=torch.float32, device=lengths.device)
     H.check(H.lib().dx_gl_noise(H.ptr(x), S, H.ptr(lengths), B, int(T), n_fft, hop, int(seed) & (2 ** 64 - 1), H.stream()))
     return x
-
-
-# ---- WAV ----------------------------------------------------------------------------------------------------------------
-
-def write_wav(path, sampling_rate, data):
-    ''' mono 64-bit IEEE-float WAV -- what `scipy.io.wavfile.write` makes of the reference's float64 waveform
-        (generate.py:137): RIFF / WAVE, `fmt ` (format 3, 18 bytes), `fact`, `data` '''
-    data = np.ascontiguousarray(np.asarray(data, dtype='<f8').reshape(-1))
-    fmt = struct.pack('<HHIIHHH', 3, 1, int(sampling_rate), int(sampling_rate) * 8, 8, 64, 0)
-    fact = struct.pack('<I', data.size)
-    body = b'WAVE' + b'fmt ' + struct.pack('<I', len(fmt)) + fmt + b'fact' + struct.pack('<I', len(fact)) + fact + \
-        b'data' + struct.pack('<I', data.nbytes)
-    with open(path, 'wb') as f:
-        f.write(b'RIFF' + struct.pack('<I', len(body) + data.nbytes) + body)
-        f.write(data.tobytes())
