@@ -125,8 +125,8 @@ int dx_conv1d_ln(const void* x, int x_dtype, long ldx, const void* w_packed, int
  * LayerNorm input of the launch that produced the stream), res_mean / res_rstd its row statistics, res_gamma / res_beta that
  * LayerNorm's parameters, and the epilogue computes  a = (s1 - mean) * rstd * gamma + beta  (0 where n >= lengths[b]) itself -- so
  * the producing launch may pass y = NULL and store only its bf16 copy and s1: 512 bytes per row less to write.  Split-K path only
- * (bf16, taps = 3, plan + fragment-order weights, B * N <= 65536); y = NULL is accepted by every path of both entry points as long
- * as y_lp is given.  res_mean = NULL: identical to dx_conv1d_ln. */
+ * (dx_conv1d_ln_path == DX_LN_PATH_SPLITK: DX_ERR_UNSUPPORTED otherwise); y = NULL is accepted by every path of both entry points
+ * as long as y_lp is given.  res_mean = NULL: identical to dx_conv1d_ln. */
 int dx_conv1d_ln_vres(const void* x, int x_dtype, long ldx, const void* w_packed, int w_dtype, const float* bias,
                       const float* residual, const float* res_mean, const float* res_rstd, const float* res_gamma, const float* res_beta,
                       const float* gamma, const float* beta, const float* film, long ldf,
@@ -145,8 +145,8 @@ int dx_conv1d_ln_vres(const void* x, int x_dtype, long ldx, const void* w_packed
  * Cout is 128 by construction.  lengths also drives the padding early-out (rows >= lengths[b] + 2 stay zero).
  * y2 (NULL = off; bf16 (B, N, 128)) with w2_packed (bf16 [1][128][128], forward packing of the map to apply): y2 = dx_pre_lp . w2^T,
  * the 128 -> 128 linear layer whose data gradient consumes dx_pre_lp next (the attention output projection, model.py:182-186),
- * computed by the epilogue from the rows it has just produced instead of by a launch of its own; needs the split-K path (bf16,
- * taps = 3, plan + w_frag, Cin % 128 == 0, B * N <= 65536: DX_ERR_UNSUPPORTED otherwise).  Same values as dx_conv1d on dx_pre_lp. */
+ * computed by the epilogue from the rows it has just produced instead of by a launch of its own; needs the split-K path
+ * (dx_conv1d_ln_path == DX_LN_PATH_SPLITK: DX_ERR_UNSUPPORTED otherwise).  Same values as dx_conv1d on dx_pre_lp. */
 int dx_conv1d_lnbwd(const void* x, int x_dtype, long ldx, const void* w_packed, int w_dtype, float* y_inout,
                     const float* s_in, const float* mean, const float* rstd, const float* gamma, const float* beta,
                     const float* film, long ldf, const int64_t* lengths, void* dx_pre_lp, float* dgamma, float* dbeta,
@@ -154,14 +154,26 @@ int dx_conv1d_lnbwd(const void* x, int x_dtype, long ldx, const void* w_packed, 
                     const int* plan, int plan_tiles, const void* w_frag, const void* w2_packed, void* y2, const DxStepScalars* step,
                     void* stream);
 
+/* Which kernel dx_conv1d_ln / dx_conv1d_ln_vres (backward = 0) or dx_conv1d_lnbwd (backward = 1) runs a GEMM on: the ONE statement
+ * of that policy -- the entry points dispatch on it and gate res_mean / y2 with it, the host side asks instead of restating it.
+ * Host-only: launches nothing, touches no device.  has_plan / has_frag: whether `plan` / `w_frag` are non-NULL.  It classifies and
+ * does not validate: what the entry points reject (a plan with fp32 operands or with taps = 1 forward, ...) they still reject.
+ *   DX_LN_PATH_SPLITK   split-K workgroups on the plan's tiles, weights from w_frag; the only path that takes res_mean and y2
+ *   DX_LN_PATH_PLAN_K3  loader-wave ring kernel on the plan's tiles, taps = 3
+ *   DX_LN_PATH_PLAN_K1  the same, taps = 1 (dx_conv1d_lnbwd only)
+ *   DX_LN_PATH_ROWS128 / DX_LN_PATH_ROWS64   fixed 128- / 64-row tiles, no plan */
+enum { DX_LN_PATH_SPLITK = 0, DX_LN_PATH_PLAN_K3 = 1, DX_LN_PATH_PLAN_K1 = 2, DX_LN_PATH_ROWS128 = 3, DX_LN_PATH_ROWS64 = 4 };
+int dx_conv1d_ln_path(int x_dtype, int w_dtype, int taps, int Cin, int B, int N, int has_plan, int has_frag, int backward);
+
 /* The weights of a k = 3 conv in MFMA-fragment order: out[chunk][tap][half][block][lane][8] = w_packed[tap][32 block + (lane & 31)]
  * [32 chunk + 16 half + 8 (lane >> 5) + 0..7], block < Cout / 32; w_packed = the [3][Cout][Cin] bf16 packing of dx_pack_conv_weight
  * (either orientation), Cin and Cout multiples of 32.  A fragment (the B operand of one v_mfma_f32_32x32x16_bf16) is one contiguous
  * KiB, so a wave reads it from L2 straight into registers with one fully coalesced load and the weights never pass through LDS.
- * Users: the optional `w_frag` of dx_conv1d_ln / dx_conv1d_lnbwd (Cout = 128, with a tile plan, Cin >= 256, Cin % 128 == 0: split-K
- * workgroups of 4 waves with 512 registers each -- all rows x 64 channels x half of the contraction per wave, accumulators in AGPRs,
- * four K chunks of fragments in flight per wave, LDS carries the activation tile only, the two K halves added through LDS in a
- * fixed order; results differ from the w_frag = NULL path by fp32 summation order only) and dx_conv1d_wide. */
+ * Users: the optional `w_frag` of dx_conv1d_ln / dx_conv1d_lnbwd (where dx_conv1d_ln_path says DX_LN_PATH_SPLITK: split-K
+ * workgroups of 4 waves with 512 registers each, accumulators in AGPRs -- tiles of up to 128 rows: every wave a quarter of the
+ * contraction for all 128 channels; 129..192 rows: half of the contraction x 64 channels per wave -- LDS carries the activation
+ * tile only, the K slices added through LDS in a fixed order; results differ from the w_frag = NULL path by fp32 summation order
+ * only), dx_conv1d_wfrag and dx_conv1d_wide. */
 int dx_pack_frag_major(const void* w_packed, void* out, int Cin, int Cout, void* stream);
 /* The same for n weights in one launch.  descs_dev: DEVICE array of n records {const void* src; void* dst; int Cin; int Cout;}
  * (dx_frag_desc_size() bytes each); max_elems = the largest Cin * Cout * 3 in the table. */

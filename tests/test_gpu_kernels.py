@@ -386,9 +386,10 @@ def test_planned_conv_ln_and_lnbwd_match_unplanned(film):
 @pytest.mark.parametrize('film', [False, True])
 @pytest.mark.parametrize('lens_list,N', [([700, 433, 257, 256, 130, 5], 700), ([1000, 999, 31, 1, 0, 640, 512, 300], 1000), ([40, 17], 40)])
 def test_splitk_conv_ln_and_lnbwd_match_ring_kernel_and_fp32_reference(film, lens_list, N):
-    ''' the split-K kernel (fragment-order weights from L2 into registers, the two K halves of a workgroup added through LDS)
-        on the balanced tiles of the ring kernel: same inputs, same dropout counters -> results equal up to the fp32 summation order
-        of the contraction (two halves instead of one chain); padding rows exact zeros; bit-reproducible; and the conv itself
+    ''' the split-K kernel (fragment-order weights from L2 into registers, the K slices of a workgroup added through LDS: four for a
+        tile of up to 128 rows, two for 129..192 rows, taller tiles are two workgroups) on the balanced tiles of the ring kernel: same
+        inputs, same dropout counters -> results equal up to the fp32 summation order of the contraction (2 or 4 partial sums instead
+        of one chain); padding rows exact zeros; bit-reproducible; and the conv itself
         against a torch fp32 reference on the same bf16-rounded operands '''
     from daft_exprt import ops
     g = torch.Generator().manual_seed(N + len(lens_list))

@@ -1111,26 +1111,33 @@ __global__ __launch_bounds__(SK_THREADS, 1) void conv_sk_kernel(ConvArgs p) {
   const int b = e.x, n0_tile = e.y, h_tile = e.z, fill_per = e.w;
   const int N = p.N, Cin = p.Cin;
   const int len = p.mask_len ? (int)p.mask_len[b] : N;
-  // a tile taller than the accumulators of the main loop hold (6 row blocks) is two workgroups' work: blockIdx.y = 1 takes the
-  // rows from 128 on (and exits at once for every other tile); the grid is (tiles, 2) there
+  // a tile taller than the accumulators of the main loop hold (SK4_MAXNA = 6 row blocks = 192 rows) is two workgroups' work:
+  // blockIdx.y = 0 takes 128 rows, blockIdx.y = 1 the rows from 128 on (and exits at once for every other tile); the grid is
+  // (tiles, 2) when N > 192
   const bool tall = h_tile > 32 * SK4_MAXNA;
   if (blockIdx.y && !tall) return;
   const int n0 = n0_tile + (int)blockIdx.y * 128, h = tall ? (blockIdx.y ? h_tile - 128 : 128) : h_tile;
   if (h > 0) {
     const TC* X = reinterpret_cast<const TC*>(p.x) + (size_t)b * N * p.ldx;
     const int nk = Cin >> 5;
-    // ---- main loop (round 6).  The contraction (Cin x 3 taps) is split FOUR ways inside the workgroup: wave w takes the 32-channel
-    // chunks 4 s + w (s = "step") with all three taps, for ALL rows of the tile (<= 5 blocks of 32) and ALL 128 output channels:
-    // <= 5 x 4 MFMA tiles = 320 accumulator registers.  Nothing is shared between the waves until the end:
-    //   * the activation slab of a wave's chunk (<= 162 rows x 32 channels, <= 11 KiB) goes through the wave's OWN 3-stage LDS-DMA
+    // ---- main loop (round 6).  The contraction (Cin x 3 taps) is split KS ways inside the workgroup, by the number NA of live 32-row
+    // blocks of the tile (the dispatch below the lambda):
+    //     NA 1..4 (<= 128 rows)    KS = 4: wave w takes the 32-channel chunks 4 s + w (s = "step") with all three taps, for ALL rows
+    //                              and ALL 128 output channels: <= 4 x 4 MFMA tiles = 256 accumulator registers
+    //     NA 5..6 (129..192 rows)  KS = 2: wave w takes the chunks 2 s + (w & 1) for all rows and the 64 channels of group w >> 1:
+    //                              <= 6 x 2 MFMA tiles = 192 accumulator registers
+    //     more than 192 rows       two workgroups (blockIdx.y, above), each with NA <= 4
+    // Nothing is shared between the waves until the end:
+    //   * the activation slab of a wave's chunk (<= 194 rows x 32 channels, 13 KiB) goes through the wave's OWN 3-stage LDS-DMA
     //     ring -- there is no workgroup barrier in the loop, only the wave's own vmcnt waits (hand-counted below);
     //   * the weight fragments (fragment order, dx_pack_frag_major: the four channel blocks of one (chunk, tap, k half) are 4 KiB
     //     contiguous) come from L2 straight into registers, every fragment read by exactly ONE wave: 786 KB per workgroup as before;
-    //   * per (tap, k half) "sub-step" a wave reads NA activation fragments from LDS for 4 NA MFMAs (0.25 KB of LDS per MFMA; the
-    //     rounds 3-5 loop: 0.5), the fragments of the next sub-step are requested before the MFMAs of this one;
-    //   * after the last step the four partial tiles of every (row block, channel block) meet through LDS, two row blocks per pass;
-    //     local channel block j of wave w is block j ^ w, so that local 0 is the one the wave keeps (static register indices) and
-    //     the sum runs in the fixed order own + (w ^ 1) + (w ^ 2) + (w ^ 3): results stay run-to-run reproducible.
+    //   * per (tap, k half) "sub-step" a wave reads NA activation fragments from LDS for KS NA MFMAs (KS = 4: 0.25 KB of LDS per
+    //     MFMA; KS = 2 and the rounds 3-5 loop: 0.5), the fragments of the next sub-step are requested before the MFMAs of this one;
+    //   * after the last step the KS partial tiles of every (row block, channel block) meet through LDS, two row blocks per pass;
+    //     local channel block j of a wave is block j ^ (its K slice) of its channel group, so that local 0 is the one the wave keeps
+    //     (static register indices) and the sum runs in the fixed order own + (w ^ 1) [+ (w ^ 2) + (w ^ 3)]: results stay run-to-run
+    //     reproducible.
     // Why: one wave per SIMD in lock step with three others (the rounds 3-5 loop: a workgroup barrier per chunk) exposes every latency.
     // Tiles of 129..160 rows (the balanced plan of a B = 48 batch: H = 124..135) also ran that loop's 8-block code path: 48 MFMAs per chunk for 30.
     f32x16 fin[SK4_MAXNA];
@@ -1846,62 +1853,63 @@ bool try_weight_stationary(const ConvArgs& a, int B, int taps, hipStream_t s) {
   }
 }
 
+// Narrow-output GEMMs (Cout <= 128, k = 3): 128-row tiles stage the weight chunk once per 128 rows (the LDS write of the
+// weight tile is the busiest part of the kernel: 818 vs 609 TFLOP/s on a dense B = 256 problem) but need enough tiles to
+// fill the chip; 64-row tiles otherwise.  Measured in the training step: B = 48 equal, B = 128 +2 % for 128 rows.
+inline int narrow_mi(int B, int N) { return (long)B * N > 64000 ? 2 : 1; }
+
+}  // namespace
+
+// Which kernel a LayerNorm-fused GEMM (Cout = 128) runs on: launch_taps switches on it, the res_mean / y2 checks of the entry points
+// and the Python host side ask it (public header).  Every condition of that choice is written here and nowhere else.
+extern "C" int dx_conv1d_ln_path(int x_dtype, int w_dtype, int taps, int Cin, int B, int N, int has_plan, int has_frag, int backward) {
+  if (has_plan && x_dtype == DX_BF16 && w_dtype == DX_BF16) {   // balanced tiles (dx_conv_tile_plan) + padding-fill workgroups
+    // split-K workgroups, weights in fragment order -- while the batch is ONE round of tiles (B * N <= 256 CUs x 256 rows): measured
+    // 0.35 % of the B = 48 step faster than the ring kernel (frame level 46 vs 50 us, phoneme level 27 vs 33 us), 2.5 % of the B = 256
+    // step slower (several rounds of 256-row tiles: the ring kernel's two epilogue teams win there).  Its main loop splits the
+    // contraction 4 (or 2 x 2 channel groups) ways in steps of 32 channels: whole 128-channel rounds, at least two of them.
+    if (taps == 3) return has_frag && Cin >= 256 && Cin % 128 == 0 && (long)B * N <= 256L * 256 ? DX_LN_PATH_SPLITK : DX_LN_PATH_PLAN_K3;
+    if (taps == 1 && backward) return DX_LN_PATH_PLAN_K1;   // k = 1 data gradient + LayerNorm backward (QKV projection, K = 384)
+  }
+  return taps == 3 && narrow_mi(B, N) == 2 ? DX_LN_PATH_ROWS128 : DX_LN_PATH_ROWS64;
+}
+#define DX_SPLITK_ONLY "the split-K path (dx_conv1d_ln_path: bf16, taps = 3, plan + fragment-order weights, Cin %% 128 == 0, B * N <= 65536)"
+
+namespace {
+
 template <typename TA, typename TC, typename TO, typename TG, int LN = 0>
 int launch_taps(const ConvArgs& a, int B, int taps, hipStream_t s) {
   const int ztiles = dx_cdiv(a.Cout, BN);
-  // Narrow-output GEMMs (Cout <= 128, k = 3): 128-row tiles stage the weight chunk once per 128 rows (the LDS write of the
-  // weight tile is the busiest part of the kernel: 818 vs 609 TFLOP/s on a dense B = 256 problem) but need enough tiles to
-  // fill the chip; 64-row tiles otherwise.  Measured in the training step: B = 48 equal, B = 128 +2 % for 128 rows.
-  const int narrow_mi = (long)B * a.N > 64000 ? 2 : 1;
   if constexpr (LN != 0) {   // LayerNorm epilogues: one channel tile (Cout = 128)
     constexpr int LNB = LN == 2 ? 3 : LN;             // backward without FiLM gradients: fewer registers
+    constexpr bool BF16 = sizeof(TA) == 2 && sizeof(TC) == 2;   // the plan paths are bf16 kernels (the classifier never names them otherwise)
     const bool film = LN == 2 && a.ln.film != nullptr;
-    if constexpr (sizeof(TA) == 2 && sizeof(TC) == 2) {
-      // split-K workgroups on the same balanced tiles, weights in fragment order -- while the batch is ONE round of tiles (B * N <= 256 CUs x
-      // 256 rows): measured 0.35 % of the B = 48 step faster than the ring kernel (frame level 46 vs 50 us, phoneme level 27 vs 33 us),
-      // 2.5 % of the B = 256 step slower (several rounds of 256-row tiles: the ring kernel's two epilogue teams win there)
-      if (a.plan && taps == 3 && a.w_frag && a.Cin >= 256 && a.Cin % 128 == 0 && (long)B * a.N <= 256L * 256) {
-        // tiles of more than 6 row blocks (possible when N > 192) are split between blockIdx.y = 0 and 1
-        dim3 gridp((unsigned)a.plan_tiles, a.N > 32 * SK4_MAXNA ? 2u : 1u);
-        if (film) hipLaunchKernelGGL((conv_sk_kernel<LN>), gridp, dim3(SK_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((conv_sk_kernel<LNB>), gridp, dim3(SK_THREADS), 0, s, a);
-        DX_LAUNCH_CHECK();
-        return DX_OK;
-      }
-      if (a.plan && taps == 3) {   // balanced 256-row tiles + padding-fill workgroups (dx_conv_tile_plan)
-        dim3 gridp((unsigned)a.plan_tiles);
-        if (film) hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 3, 4, 32, LN, DX_PLAN_RING>), gridp, dim3(2 * NTHREADS), 0, s, a);
-        else hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 3, 4, 32, LNB, DX_PLAN_RING>), gridp, dim3(2 * NTHREADS), 0, s, a);
-        DX_LAUNCH_CHECK();
-        return DX_OK;
-      }
-      if constexpr (LN == 2) {
-        if (a.plan && taps == 1) {   // k = 1 data gradient + LayerNorm backward (QKV projection, K = 384) on the same tiles
-          dim3 gridp((unsigned)a.plan_tiles);
-          if (film) hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 1, 4, 32, LN, 3>), gridp, dim3(2 * NTHREADS), 0, s, a);
-          else hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 1, 4, 32, LNB, 3>), gridp, dim3(2 * NTHREADS), 0, s, a);
-          DX_LAUNCH_CHECK();
-          return DX_OK;
-        }
-      }
+    const dim3 plan_grid((unsigned)a.plan_tiles), plan_block(2 * NTHREADS), block(NTHREADS);
+    auto fixed_grid = [&](int rows) { return dim3((unsigned)((((long)dx_cdiv(a.N, rows) * B + 7) / 8) * 8)); };
+#define DX_LN_LAUNCH(grid, block, ...)                                                               \
+  do {                                                                                               \
+    if (film) { constexpr int LNX = LN; hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, s, a); }   \
+    else { constexpr int LNX = LNB; hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, s, a); }       \
+  } while (0)
+    switch (dx_conv1d_ln_path(sizeof(TA) == 2 ? DX_BF16 : DX_F32, sizeof(TC) == 2 ? DX_BF16 : DX_F32, taps, a.Cin, B, a.N, a.plan != nullptr,
+                              a.w_frag != nullptr, LN == 2)) {
+      case DX_LN_PATH_SPLITK:   // tiles of more than 192 rows (possible when N > 192) are split between blockIdx.y = 0 and 1
+        if constexpr (BF16) DX_LN_LAUNCH(dim3((unsigned)a.plan_tiles, a.N > 32 * SK4_MAXNA ? 2u : 1u), dim3(SK_THREADS), conv_sk_kernel<LNX>);
+        break;
+      case DX_LN_PATH_PLAN_K3:
+        if constexpr (BF16) DX_LN_LAUNCH(plan_grid, plan_block, conv_gemm_kernel<TA, TC, TO, TG, 3, 4, 32, LNX, DX_PLAN_RING>);
+        break;
+      case DX_LN_PATH_PLAN_K1:
+        if constexpr (BF16 && LN == 2) DX_LN_LAUNCH(plan_grid, plan_block, conv_gemm_kernel<TA, TC, TO, TG, 1, 4, 32, LNX, 3>);
+        break;
+      case DX_LN_PATH_ROWS128:
+        DX_LN_LAUNCH(fixed_grid(128), block, conv_gemm_kernel<TA, TC, TO, TG, 3, 2, 32, LNX>);
+        break;
+      default:                  // DX_LN_PATH_ROWS64
+        if (taps == 1) DX_LN_LAUNCH(fixed_grid(64), block, conv_gemm_kernel<TA, TC, TO, TG, 1, 1, CG_K1_BK, LNX>);
+        else DX_LN_LAUNCH(fixed_grid(64), block, conv_gemm_kernel<TA, TC, TO, TG, 3, 1, 32, LNX>);
     }
-    if (narrow_mi == 2 && taps == 3) {
-      const long pt2 = (long)dx_cdiv(a.N, 128) * B;
-      dim3 grid2((unsigned)(((pt2 + 7) / 8) * 8));
-      if (film) hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 3, 2, 32, LN>), grid2, dim3(NTHREADS), 0, s, a);
-      else hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 3, 2, 32, LNB>), grid2, dim3(NTHREADS), 0, s, a);
-      DX_LAUNCH_CHECK();
-      return DX_OK;
-    }
-    const long ptiles = (long)dx_cdiv(a.N, 64) * B;
-    dim3 grid((unsigned)(((ptiles + 7) / 8) * 8)), block(NTHREADS);
-    if (taps == 1) {
-      if (film) hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 1, 1, CG_K1_BK, LN>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 1, 1, CG_K1_BK, LNB>), grid, block, 0, s, a);
-    } else {
-      if (film) hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 3, 1, 32, LN>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_gemm_kernel<TA, TC, TO, TG, 3, 1, 32, LNB>), grid, block, 0, s, a);
-    }
+#undef DX_LN_LAUNCH
     DX_LAUNCH_CHECK();
     return DX_OK;
   } else {
@@ -1911,7 +1919,7 @@ int launch_taps(const ConvArgs& a, int B, int taps, hipStream_t s) {
     // and a taller tile re-uses the taps x 128-channel weight chunk for twice the positions: 930 vs 810 TFLOP/s.
     static int forced_wide = getenv("DX_CONV_WIDE_MI") ? atoi(getenv("DX_CONV_WIDE_MI")) : 0;
     const int wide_mi = forced_wide ? forced_wide : ((long)dx_cdiv(a.N, 256) * B * ztiles >= 1024 ? 4 : 2);
-    const int mi = ztiles == 1 ? (taps == 3 ? narrow_mi : 1) : ((taps == 3 && a.Cin >= 512 && sizeof(TC) == 2) ? wide_mi : 2);
+    const int mi = ztiles == 1 ? (taps == 3 ? narrow_mi(B, a.N) : 1) : ((taps == 3 && a.Cin >= 512 && sizeof(TC) == 2) ? wide_mi : 2);
     const long ptiles = (long)dx_cdiv(a.N, 64 * mi) * B;
     dim3 grid((unsigned)(((ptiles + 7) / 8) * 8 * ztiles)), block(NTHREADS);
     if constexpr (sizeof(TC) == 2) {
@@ -2126,13 +2134,12 @@ extern "C" int dx_conv1d_ln_vres(const void* x, int x_dtype, long ldx, const voi
                                  const int64_t* lengths, float* y, void* y_lp, float* s_out, float* mean, float* rstd, int B, int N,
                                  int Cin, int taps, float p_pre, uint64_t seed_pre, const int* plan, int plan_tiles, const void* w_frag,
                                  const void* w2_packed, const float* b2, void* y2, int n2, const DxStepScalars* step, void* stream) {
+  const int path = dx_conv1d_ln_path(x_dtype, w_dtype, taps, Cin, B, N, plan != nullptr, w_frag != nullptr, 0);
   DX_REQUIRE(x && w_packed && residual && gamma && beta && (y || y_lp), DX_ERR_ARG, "dx_conv1d_ln: null pointer");
   DX_REQUIRE(y || (x_dtype == DX_BF16 && w_dtype == DX_BF16), DX_ERR_ARG, "dx_conv1d_ln: y = NULL (bf16 copy only) goes with bf16 operands");
   if (res_mean) {
     DX_REQUIRE(res_rstd && res_gamma && res_beta && lengths, DX_ERR_ARG, "dx_conv1d_ln_vres: res_mean / res_rstd / res_gamma / res_beta / lengths come together");
-    DX_REQUIRE(plan && w_frag && taps == 3 && Cin >= 256 && Cin % 128 == 0 && (long)B * N <= 256L * 256 && w_dtype == DX_BF16 && x_dtype == DX_BF16,
-               DX_ERR_UNSUPPORTED, "dx_conv1d_ln_vres: the re-derived residual exists on the split-K path only (bf16, taps = 3, plan + fragment-order "
-               "weights, Cin %% 128 == 0, B * N <= 65536)");
+    DX_REQUIRE(path == DX_LN_PATH_SPLITK, DX_ERR_UNSUPPORTED, "dx_conv1d_ln_vres: the re-derived residual needs " DX_SPLITK_ONLY);
   }
   DX_REQUIRE(!w_frag || plan, DX_ERR_ARG, "dx_conv1d_ln: fragment-order weights go with a tile plan");
   if (int rc = plan_check("dx_conv1d_ln", plan, plan_tiles, lengths, x_dtype, w_dtype, ldx, Cin, taps, B, N)) return rc;
@@ -2145,10 +2152,9 @@ extern "C" int dx_conv1d_ln_vres(const void* x, int x_dtype, long ldx, const voi
              LNEpi{gamma, beta, residual, film, ldf, y, y_lp, s_out, mean, rstd, p_pre, seed_pre, 1}};
   a.plan = plan; a.plan_tiles = plan_tiles; a.w_frag = w_frag; a.ln.step = step;
   a.ln.res_mean = res_mean; a.ln.res_rstd = res_rstd; a.ln.res_gamma = res_gamma; a.ln.res_beta = res_beta;
-  if (y2) {   // second GEMM in the epilogue (the next block's QKV projection): only the split-K workgroups carry it (gate of launch_taps)
-    DX_REQUIRE(w2_packed && (n2 == 128 || n2 == 384) && plan && w_frag && taps == 3 && Cin >= 256 && Cin % 128 == 0 && (long)B * N <= 256L * 256 &&
-               w_dtype == DX_BF16 && x_dtype == DX_BF16, DX_ERR_UNSUPPORTED, "dx_conv1d_ln: y2 needs n2 in {128, 384} and the split-K path (bf16, "
-               "taps = 3, plan + fragment-order weights, Cin %% 128 == 0, B * N <= 65536)");
+  if (y2) {   // second GEMM in the epilogue (the next block's QKV projection): only the split-K workgroups carry it
+    DX_REQUIRE(w2_packed && (n2 == 128 || n2 == 384) && path == DX_LN_PATH_SPLITK, DX_ERR_UNSUPPORTED,
+               "dx_conv1d_ln: y2 needs n2 in {128, 384} and " DX_SPLITK_ONLY);
     a.ln.w2 = w2_packed; a.ln.y2 = y2; a.ln.b2 = b2; a.ln.n2 = n2;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -2178,10 +2184,9 @@ extern "C" int dx_conv1d_lnbwd(const void* x, int x_dtype, long ldx, const void*
              LNEpi{gamma, beta, nullptr, film, ldf, y_inout, dx_pre_lp, const_cast<float*>(s_in), const_cast<float*>(mean),
                    const_cast<float*>(rstd), p_pre, seed_pre, 2, dgamma, dbeta, dfilm, lddf}};
   a.plan = plan; a.plan_tiles = plan_tiles; a.w_frag = w_frag; a.ln.step = step;
-  if (y2) {   // second GEMM in the epilogue: only the split-K workgroups carry it (same gate as launch_taps)
-    DX_REQUIRE(w2_packed && plan && w_frag && taps == 3 && Cin >= 256 && Cin % 128 == 0 && (long)B * N <= 256L * 256 && w_dtype == DX_BF16 &&
-               x_dtype == DX_BF16, DX_ERR_UNSUPPORTED, "dx_conv1d_lnbwd: y2 needs the split-K path (bf16, taps = 3, plan + fragment-order weights, "
-               "Cin %% 128 == 0, B * N <= 65536)");
+  if (y2) {   // second GEMM in the epilogue: only the split-K workgroups carry it
+    DX_REQUIRE(w2_packed && dx_conv1d_ln_path(x_dtype, w_dtype, taps, Cin, B, N, plan != nullptr, w_frag != nullptr, 1) == DX_LN_PATH_SPLITK,
+               DX_ERR_UNSUPPORTED, "dx_conv1d_lnbwd: y2 needs " DX_SPLITK_ONLY);
     a.ln.w2 = w2_packed; a.ln.y2 = y2; a.ln.b2 = nullptr; a.ln.n2 = BN;
   }
   hipStream_t s = (hipStream_t)stream;

@@ -374,9 +374,9 @@ class DaftExprt(nn.Module):
                     bwd.append((w, self._packed['T:' + name], True))
             self._pack_fwd = [ops.pack_table(f, dev) if f else None for f in fwd]   # [pre-net, everything else]
             self._pack_bwd = ops.pack_table(bwd, dev)
-            # fragment-order copies ('F:' / 'FT:' + name) of the k = 3 weights whose GEMM ends in a 128-channel LayerNorm epilogue
-            # on balanced tiles (second FF conv forward; first FF conv data gradient): the split-K kernel reads them from L2
-            # straight into registers, one contiguous KiB per MFMA fragment
+            # fragment-order copies ('F:' of the forward matrix, 'FT:' of the data-gradient matrix) of the k = 3 weights, one contiguous KiB
+            # per MFMA fragment: a matrix gets one exactly when a kernel that reads fragments from L2 straight into registers takes its
+            # (Cin, Cout) -- the wide kernel, the register-weights kernel or the split-K workgroups (the predicates of ops)
             self._frag_fwd, self._frag_bwd = [None, None], None
             if self.cd == torch.bfloat16:
                 ffwd, fbwd = ([], []), []
@@ -384,24 +384,17 @@ class DaftExprt(nn.Module):
                     w = self._P[name]
                     if w.dim() != 3 or w.shape[2] != 3:
                         continue
-                    if w.shape[0] % 256 == 0 and w.shape[1] % 128 == 0 and w.shape[1] >= 256:     # wide GEMMs (pre-net 1024 -> 1024): dx_conv1d_wide
+                    # The wide kernel goes by shape alone.  The other two are handed a copy by the FF blocks only: a pre-net or predictor conv
+                    # of a matching shape (128 -> 256, k = 3) passes W.get('F:...') to ops.conv1d, which would hand the copy to
+                    # dx_conv1d_wfrag -- another load path for that GEMM
+                    is_ff = '.feed_forward.convs.' in name
+                    reads = lambda cin, cout: ops.wide_shape_ok(cin, cout) or (
+                        is_ff and (ops.wreg_shape_ok(cin, cout) or ops.splitk_shape_ok(cin, cout)))
+                    cout, cin = w.shape[0], w.shape[1]
+                    if reads(cin, cout):
                         self._packed['F:' + name] = torch.empty(w.numel(), dtype=self.cd, device=dev)
                         ffwd[0 if early(name) else 1].append((self._packed[name], self._packed['F:' + name]))
-                        if w.shape[1] % 256 == 0 and w.shape[0] % 128 == 0:
-                            self._packed['FT:' + name] = torch.empty(w.numel(), dtype=self.cd, device=dev)
-                            fbwd.append((self._packed['T:' + name], self._packed['FT:' + name]))
-                    if name.endswith('feed_forward.convs.2.conv.weight') and w.shape[0] == 128 and w.shape[1] % 32 == 0 and w.shape[1] >= 256:
-                        self._packed['F:' + name] = torch.empty(w.numel(), dtype=self.cd, device=dev)
-                        ffwd[0 if early(name) else 1].append((self._packed[name], self._packed['F:' + name]))
-                    if name.endswith('feed_forward.convs.0.conv.weight') and w.shape[1] == 128 and w.shape[0] % 32 == 0 and w.shape[0] >= 256:
-                        self._packed['FT:' + name] = torch.empty(w.numel(), dtype=self.cd, device=dev)
-                        fbwd.append((self._packed['T:' + name], self._packed['FT:' + name]))
-                    # the register-weights kernel (Cin = 128 -> Cout % 256 == 0: first FF conv forward, second FF conv data gradient)
-                    # loads its weight slice fragment by fragment from the same layout
-                    if name.endswith('feed_forward.convs.0.conv.weight') and w.shape[1] == 128 and w.shape[0] % 256 == 0:
-                        self._packed['F:' + name] = torch.empty(w.numel(), dtype=self.cd, device=dev)
-                        ffwd[0 if early(name) else 1].append((self._packed[name], self._packed['F:' + name]))
-                    if name.endswith('feed_forward.convs.2.conv.weight') and w.shape[0] == 128 and w.shape[1] % 256 == 0:
+                    if 'T:' + name in self._packed and reads(cout, cin):
                         self._packed['FT:' + name] = torch.empty(w.numel(), dtype=self.cd, device=dev)
                         fbwd.append((self._packed['T:' + name], self._packed['FT:' + name]))
                 self._frag_fwd = [ops.frag_table(f, dev) if f else None for f in ffwd]

@@ -95,12 +95,43 @@ def pack_conv_weight(w, dtype, transpose_flip=False, out=None):
     return out
 
 
+# Which kernel a GEMM runs on is decided in csrc/conv_gemm.hip.  For the LayerNorm-fused GEMMs `ln_path` asks that decision
+# (dx_conv1d_ln_path) and nothing here restates it.  The wide and the register-weights kernel have no host query: their shape rules are
+# stated once each below (tests/test_gpu_conv.py asserts the predicates and then runs the entry points, which check the same on their side).
+LN_SPLITK, LN_PLAN_K3, LN_PLAN_K1, LN_ROWS128, LN_ROWS64 = range(5)    # DX_LN_PATH_* of include/daft_exprt_hip.h
+_LN_PATHS = {}
+
+
+def ln_path(x_dtype, w_dtype, taps, Cin, B, N, has_plan, has_frag, backward=False):
+    ''' the kernel path of conv1d_ln (backward: conv1d_lnbwd) for these arguments (a pure function of them: remembered, as
+        `wgrad_ws_floats`) '''
+    key = (x_dtype, w_dtype, taps, Cin, B, N, has_plan, has_frag, backward)
+    v = _LN_PATHS.get(key)
+    if v is None:
+        v = _LN_PATHS[key] = H.lib().dx_conv1d_ln_path(H._DT[x_dtype], H._DT[w_dtype], taps, Cin, B, N, int(has_plan), int(has_frag),
+                                                       int(backward))
+    return v
+
+
+def splitk_shape_ok(Cin, Cout):
+    ''' k = 3 weights the split-K workgroups can take (while the batch is small enough): the shapes whose fragment-order copy is read '''
+    return Cout == 128 and ln_path(torch.bfloat16, torch.bfloat16, 3, Cin, 1, 1, True, True) == LN_SPLITK
+
+
+def wide_shape_ok(Cin, Cout):
+    ''' k = 3 shapes of the wide kernel (dx_conv1d_wide) '''
+    return Cin % 128 == 0 and Cin >= 256 and Cout % 256 == 0
+
+
+def wreg_shape_ok(Cin, Cout):
+    ''' shapes of the register-weights kernel (dx_conv1d_wfrag with a copy, dx_conv1d_relu_bits) '''
+    return Cin == 128 and Cout % 256 == 0
 
 
 def relu_bits_ok(x, w_packed, out_dtype=None):
     ''' the shapes `conv1d(..., relu_bits=True)` / a bit-mask `relu_gate` take: the register-weights kernel (dx_conv1d_relu_bits) '''
     taps, Cout, Cin = w_packed.shape
-    return (x.is_cuda and taps == 3 and Cin == 128 and Cout % 256 == 0 and x.dtype == torch.bfloat16 and w_packed.dtype == torch.bfloat16
+    return (x.is_cuda and taps == 3 and wreg_shape_ok(Cin, Cout) and x.dtype == torch.bfloat16 and w_packed.dtype == torch.bfloat16
             and (out_dtype or x.dtype) == torch.bfloat16 and x.stride(1) % 8 == 0)
 
 
@@ -121,7 +152,7 @@ def conv1d(x, w_packed, bias=None, out_dtype=None, relu=False, relu_gate=None, m
     out_dtype = out_dtype or x.dtype
     if (w_frag is not None and wide_plan is not None and taps == 3 and x.dtype == torch.bfloat16 and out_dtype == torch.bfloat16
             and out is None and relu_gate is None and mask_lengths is None and skip_lengths is not None and not transposed_out
-            and Cin % 128 == 0 and Cin >= 256 and Cout % 256 == 0):
+            and wide_shape_ok(Cin, Cout)):
         table, pb, pn = wide_plan
         assert (pb, pn) == (B, N), 'tile plan built for another batch geometry'
         y = _empty((B, N, Cout), dtype=torch.bfloat16, device=x.device)
@@ -129,6 +160,10 @@ def conv1d(x, w_packed, bias=None, out_dtype=None, relu=False, relu_gate=None, m
             H.check(H.lib().dx_conv1d_wide(H.ptr(x), x.stride(1), H.ptr(w_frag), H.ptr(bias), H.ptr(y), y.stride(1), H.ptr(skip_lengths),
                                            H.ptr(table), table.shape[0], 2, B, N, Cin, Cout, H.CONV_RELU if relu else 0, H.stream()))
         return y
+    frag = None
+    if w_frag is not None and taps == 3 and wreg_shape_ok(Cin, Cout) and w_packed.dtype == torch.bfloat16:
+        assert w_frag.dtype == torch.bfloat16 and w_frag.numel() == w_packed.numel()
+        frag = w_frag                                 # register-weights kernel: fragments straight into registers
     gate_bits = relu_gate is not None and relu_gate.dtype == torch.int32
     if relu_bits or gate_bits:
         assert relu_bits_ok(x, w_packed, out_dtype) and out is None and not transposed_out and not accumulate and relu == bool(relu_bits) and \
@@ -136,7 +171,6 @@ def conv1d(x, w_packed, bias=None, out_dtype=None, relu=False, relu_gate=None, m
         y = _empty((B, N, Cout), dtype=torch.bfloat16, device=x.device)
         bits = relu_gate if gate_bits else _empty((B, Cout // 32, N), dtype=torch.int32, device=x.device)
         assert tuple(bits.shape) == (B, Cout // 32, N) and bits.is_contiguous()
-        frag = w_frag if (w_frag is not None and w_frag.dtype == torch.bfloat16 and w_frag.numel() == w_packed.numel()) else None
         with _probe('conv_gemm', lambda: 2. * B * N * Cin * Cout * taps, N):
             H.check(H.lib().dx_conv1d_relu_bits(H.ptr(x), x.stride(1), H.ptr(w_packed), H.ptr(frag), H.ptr(bias), H.ptr(y), y.stride(1),
                                                 None if gate_bits else H.ptr(bits), H.ptr(bits) if gate_bits else None,
@@ -146,10 +180,6 @@ def conv1d(x, w_packed, bias=None, out_dtype=None, relu=False, relu_gate=None, m
         assert not accumulate
         out = _empty((B, Cout, N) if transposed_out else (B, N, Cout), dtype=out_dtype, device=x.device)
     flags = (H.CONV_RELU if relu else 0) | (H.CONV_TRANSPOSED_OUT if transposed_out else 0) | (4 if accumulate else 0)
-    frag = None
-    if w_frag is not None and taps == 3 and Cin == 128 and w_packed.dtype == torch.bfloat16:
-        assert w_frag.dtype == torch.bfloat16 and w_frag.numel() == w_packed.numel()
-        frag = w_frag                                 # register-weights kernel: fragments straight into registers (dx_conv1d_wfrag)
     with _probe('conv_gemm', lambda: 2. * B * N * Cin * Cout * taps, N):
       H.check(H.lib().dx_conv1d_wfrag(H.ptr(x), H.dt(x), x.stride(1), H.ptr(w_packed), H.dt(w_packed), H.ptr(frag), H.ptr(bias),
                                     H.ptr(out), H.dt(out), out.stride(1), H.ptr(relu_gate),
@@ -160,10 +190,9 @@ def conv1d(x, w_packed, bias=None, out_dtype=None, relu=False, relu_gate=None, m
 
 def splitk_ln_ok(B, N, x_dtype, w_packed, plan, w_frag):
     ''' does conv1d_ln on a (B, N, Cin) input of x_dtype with these weights run on the split-K workgroups (the path that can take
-        `residual_ln`)?  Mirrors the gate of `launch_taps` in csrc/conv_gemm.hip '''
-    Cin = w_packed.shape[2]
-    return (USE_SPLITK and plan is not None and w_frag is not None and x_dtype == torch.bfloat16 and w_packed.dtype == torch.bfloat16
-            and w_packed.shape[0] == 3 and Cin >= 256 and Cin % 128 == 0 and B * N <= 65536 and tuple(plan[1:]) == (B, N))
+        `residual_ln`)? '''
+    return (USE_SPLITK and plan is not None and w_frag is not None and tuple(plan[1:]) == (B, N) and
+            ln_path(x_dtype, w_packed.dtype, w_packed.shape[0], w_packed.shape[2], B, N, True, True) == LN_SPLITK)
 
 
 def conv1d_ln(x, w_packed, bias, residual, gamma, beta, lengths, film=None, save=False, p_pre=0., seed_pre=0, lp_copy=False, plan=None,
@@ -186,13 +215,13 @@ def conv1d_ln(x, w_packed, bias, residual, gamma, beta, lengths, film=None, save
     s_out = _empty((B, N, 128), dtype=torch.float32, device=dev) if save else None
     mean = _empty(B * N, dtype=torch.float32, device=dev) if save else None
     rstd = _empty(B * N, dtype=torch.float32, device=dev) if save else None
-    pargs = _plan_args(plan, x, w_packed, B, N, w_frag=w_frag)
+    *pargs, path = _plan_args(plan, x, w_packed, B, N, w_frag=w_frag)
     r_mean = r_rstd = r_gamma = r_beta = None
     if residual_ln is not None:
         assert splitk_ln_ok(B, N, x.dtype, w_packed, plan, w_frag), 'residual_ln: split-K path only'
         r_mean, r_rstd, r_gamma, r_beta = residual_ln
     y2, n2 = None, 0
-    if (w2_packed is not None and lp_copy and pargs[2] is not None and taps == 3 and Cin % 128 == 0 and B * N <= 65536
+    if (w2_packed is not None and lp_copy and path == LN_SPLITK
             and w2_packed.dtype == torch.bfloat16 and w2_packed.shape[0] == 1 and w2_packed.shape[2] == 128 and w2_packed.shape[1] in (128, 384)):
         n2 = w2_packed.shape[1]
         y2 = _empty((B, N, n2), dtype=torch.bfloat16, device=dev)
@@ -221,10 +250,9 @@ def conv1d_lnbwd(x, w_packed, y_inout, s_in, mean, rstd, gamma, beta, lengths, d
     dx_lp = _empty((B, N, 128), dtype=torch.bfloat16, device=x.device)
     ldf = film.stride(0) if film is not None else 0
     lddf = dfilm.stride(0) if dfilm is not None else 0
-    pargs = _plan_args(plan, x, w_packed, B, N, k1_ok=True, w_frag=w_frag)
+    *pargs, path = _plan_args(plan, x, w_packed, B, N, backward=True, w_frag=w_frag)
     y2 = None
-    if (w2_packed is not None and pargs[2] is not None and taps == 3 and Cin % 128 == 0 and B * N <= 65536
-            and w2_packed.dtype == torch.bfloat16 and tuple(w2_packed.shape) == (1, 128, 128)):
+    if w2_packed is not None and path == LN_SPLITK and w2_packed.dtype == torch.bfloat16 and tuple(w2_packed.shape) == (1, 128, 128):
         y2 = _empty((B, N, 128), dtype=torch.bfloat16, device=x.device)
     with _probe('conv_gemm', lambda: 2. * B * N * Cin * Cout * taps + (2. * B * N * 128 * 128 if y2 is not None else 0.), N):
         H.check(H.lib().dx_conv1d_lnbwd(H.ptr(x), H.dt(x), x.stride(1), H.ptr(w_packed), H.dt(w_packed), H.ptr(y_inout), H.ptr(s_in),
@@ -273,20 +301,22 @@ def batch_prep(lengths, N, plan=True, wide=True, order=True):
     return (t0, B, N) if plan else None, (t2, B, N) if wide else None, od
 
 
-def _plan_args(plan, x, w_packed, B, N, k1_ok=False, w_frag=None):
-    ''' (table pointer, n_tiles, fragment-order weights) when the plan applies to this GEMM (bf16 operands, k = 3, same batch
-        geometry); the fragment-order copy only goes with a plan, k = 3 and Cin >= 256 '''
-    taps = w_packed.shape[0]
-    if plan is None or x.dtype != torch.bfloat16 or w_packed.dtype != torch.bfloat16 or x.shape[2] % 32 or \
-            not (taps == 3 or (taps == 1 and k1_ok and x.shape[2] >= 256)):
-        return None, 0, None
+def _plan_args(plan, x, w_packed, B, N, backward=False, w_frag=None):
+    ''' (table pointer, n_tiles, fragment-order weights, kernel path) of a LayerNorm-fused GEMM.  The plan is passed when a plan path
+        takes this GEMM (`ln_path`; whole 32-channel chunks; k = 1 from Cin = 256 on), the copy with it wherever the split-K workgroups
+        can read it -- whether they run is decided per batch: the path, which is None without a plan '''
+    taps, _, Cin = w_packed.shape
+    want_frag = w_frag is not None and USE_SPLITK
+    path = ln_path(x.dtype, w_packed.dtype, taps, Cin, B, N, True, want_frag, backward) if plan is not None else None
+    if path not in (LN_SPLITK, LN_PLAN_K3, LN_PLAN_K1) or Cin % 32 or (path == LN_PLAN_K1 and Cin < 256):
+        return None, 0, None, None
     table, pb, pn = plan
     assert (pb, pn) == (B, N), 'tile plan built for another batch geometry'
     frag = None
-    if w_frag is not None and taps == 3 and x.shape[2] >= 256 and USE_SPLITK:
+    if want_frag and taps == 3 and splitk_shape_ok(Cin, w_packed.shape[1]):
         assert w_frag.dtype == torch.bfloat16 and w_frag.numel() == w_packed.numel()
         frag = H.ptr(w_frag)
-    return H.ptr(table), table.shape[0], frag
+    return H.ptr(table), table.shape[0], frag, path
 
 
 USE_SPLITK = True   # False: the LayerNorm-fused k = 3 GEMMs stay on the ring kernel (tests compare the two)
@@ -404,7 +434,6 @@ def wgrad_ws_floats(B, N, Cin, Cout, taps):
     if v is None:
         v = _WS_FLOATS[key] = H.lib().dx_conv1d_wgrad_ws_floats(B, N, Cin, Cout, taps)
     return v
-
 
 
 # ----------------------------------------------------------------------------- LayerNorm (+ residual, dropout, FiLM, mask)
