@@ -563,6 +563,31 @@ int dx_resample(const float* x, long ldx, const int64_t* n_in, const float* bank
 int dx_ft_pack(const float* mel, long ld_mb, long ld_mk, const int64_t* lengths, int B, int n_mel, int T, const float* wav,
                long ldw, const int64_t* crop, long S, float* mel_out, int16_t* wav_out, void* stream);
 
+/* ---- K20: pitch tracking (stands in for extract_features.py:222-269, which runs a prebuilt REAPER binary; not a port of it:
+ * tests/pitch_oracle.py defines the arithmetic, DESIGN 9d the algorithm and its constants).  Additive entry points.
+ *
+ * dx_pitch_candidates: wav (B, ldw) fp32 with n_samples[b] <= S samples per row.  Analysis frame a < A_b = 1 + floor(n_b / step)
+ * (step = sr * f0_interval samples, a double) is centred on sample floor(a * step + 0.5); its normalised cross-correlation
+ *     r(k) = sum_{i < window} x[s + i] x[s + k + i] / (sqrt(e(0) e(k)) + floor),   s = centre - window / 2,  x = 0 outside [0, n_b)
+ * over lags lag_min - 1 .. lag_max + 1 has its cross term summed in fp32 in tap order, e(k) = the energy of the lagged window
+ * (from one running sum of squares, in double) and floor = window * (1e-2 * mean(x^2) + 1e-10).  cand_lag / cand_val (B, A, K),
+ * K = dx_pitch_num_candidates(): the up to K largest local maxima above 0.3 at lags lag_min .. lag_max, lag and value
+ * interpolated through their neighbours, in order of value (then of lag); empty slots and frames a >= A_b are 0.
+ * mean_sq: B doubles of scratch.  A >= 1 + floor(S / step); window + lag_max + 1 > 2048: DX_ERR_UNSUPPORTED.
+ *
+ * dx_pitch_viterbi: the cheapest path per utterance over the K candidates and one unvoiced state per analysis frame.
+ * back ((B, A, K + 1) bytes) and hz ((B, A) floats: sr / lag along the path, 0 where unvoiced or a >= A_b) are scratch and
+ * by-product; log_pitch (B, T), T >= 1 + S / hop: mel frame t < n_frames[b] = 1 + n_b / hop takes analysis frame
+ * min(floor(t * hop / step + 0.5), A_b - 1) and holds log(Hz), 0 where unvoiced and for t >= n_frames[b].  uv_cost scales the
+ * cost of the unvoiced state (hparams.uv_cost). */
+int dx_pitch_num_candidates(void);
+int dx_pitch_candidates(const float* wav, long ldw, const int64_t* n_samples, double* mean_sq, float* cand_lag,
+                        float* cand_val, int B, long S, int A, double step, int window, int lag_min, int lag_max,
+                        void* stream);
+int dx_pitch_viterbi(const float* cand_lag, const float* cand_val, const int64_t* n_samples, unsigned char* back, float* hz,
+                     float* log_pitch, int64_t* n_frames, int B, long S, int A, int T, int sr, double step, int hop,
+                     int lag_max, float uv_cost, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

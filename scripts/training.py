@@ -5,7 +5,7 @@ sub-commands:
     python scripts/training.py -en EXP -dd DATA_DIR -spks SPK [SPK ...] -lg english fine_tune -chk CKPT
 It builds `HyperParams`, writes `<experiment>/config.json` and runs `daft_exprt/train.py` or `daft_exprt/fine_tune.py` in a
 sub-process, like the reference (`training.py:101-128`).  `pre_process` is dataset tooling outside the accelerated path
-(Montreal Forced Aligner, REAPER)."""
+(its markers come from the Montreal Forced Aligner)."""
 import argparse
 import os
 import subprocess
@@ -73,7 +73,7 @@ def parse_args(argv=None):
 if __name__ == '__main__':
     args = parse_args()
     if args.command not in ('train', 'fine_tune'):
-        sys.exit(f'"{args.command}" is dataset tooling of the reference (MFA / librosa / REAPER); only "train" and "fine_tune" '
+        sys.exit(f'"{args.command}" is dataset tooling of the reference (its markers come from MFA); only "train" and "fine_tune" '
                  'are accelerated here')
     out_dir, config_file, log_file = experiment_paths(args)
     hparams = build_hparams(args, out_dir)

@@ -2,17 +2,24 @@
 330-359`; callers `generate.py:455-457`, `extract_features.py:429, 465-466`, `fine_tune.py:102`).
 
 `mel_spectrogram_HiFi(wav, hparams)` and `extract_energy(mel_spec)` keep the reference's signatures (NumPy in, NumPy
-out, one utterance); `mel_spectrogram_batch` is the batched device entry.  The mel filterbank is built here from the
+out, one utterance); `mel_spectrogram_batch` is the batched device entry.  `extract_pitch(wav, fs, hparams)` keeps the
+signature of `extract_features.py:222-269` and `pitch_batch` is its batched device entry, but the tracker behind them is this
+project's own (csrc/pitch.hip), not the REAPER binary the reference runs.  The mel filterbank is built here from the
 published Slaney formula (what `librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax)` computes with its defaults
 htk=False, norm='slaney'); librosa itself is not a dependency.  No CPU fallback: without the HIP library / a GPU these
 functions raise.
 """
+import math
+
 import numpy as np
 import torch
 
 from daft_exprt import _hip as H
 from daft_exprt.audio import fft_tables
 from daft_exprt.audio import rescale_wav_to_float32  # noqa: F401  (the reference keeps it here, `extract_features.py:362`)
+
+
+PITCH_WINDOW_S = 0.015     # correlation window of the pitch tracker (DESIGN 9d)
 
 
 def _hz_to_mel(f):
@@ -89,6 +96,74 @@ def mel_spectrogram_HiFi(wav, hparams, device='cuda:0'):
     n = torch.tensor([w.shape[1]], dtype=torch.int64, device=device)
     mel, _, nfr = mel_spectrogram_batch(w, n, hparams)
     return mel[0, :, :int(nfr[0])].cpu().numpy()
+
+
+def pitch_geometry(hparams, sr=None):
+    ''' (sr, step = samples per analysis frame, window, lag_min, lag_max) of the pitch tracker at rate `sr` (default
+        hparams.sampling_rate): a 15 ms window and the lags floor(sr / max_f0) .. ceil(sr / min_f0) '''
+    sr = int(hparams.sampling_rate if sr is None else sr)
+    lag_min, lag_max = int(math.floor(sr / float(hparams.max_f0))), int(math.ceil(sr / float(hparams.min_f0)))
+    if not 2 <= lag_min < lag_max:
+        raise ValueError(f'pitch: min_f0={hparams.min_f0}, max_f0={hparams.max_f0} give no lag range at {sr} Hz')
+    return sr, float(sr) * float(hparams.f0_interval), int(round(PITCH_WINDOW_S * sr)), lag_min, lag_max
+
+
+def pitch_candidates_batch(wavs, n_samples, hparams, sr=None):
+    ''' `dx_pitch_candidates`: (lags, values), each (B, A, K) fp32 on the device, A = 1 + floor(S / step): per analysis frame the
+        up to K best maxima of the normalised cross-correlation, in order of value; empty slots are 0 '''
+    H.require_gpu(wavs, n_samples)
+    assert wavs.dtype == torch.float32 and wavs.dim() == 2 and wavs.stride(1) == 1 and n_samples.dtype == torch.int64
+    sr, step, window, lag_min, lag_max = pitch_geometry(hparams, sr)
+    B, S = wavs.shape
+    A = 1 + int(math.floor(S / step))
+    K = int(H.lib().dx_pitch_num_candidates())
+    dev = wavs.device
+    lags = torch.empty((B, A, K), dtype=torch.float32, device=dev)
+    vals = torch.empty((B, A, K), dtype=torch.float32, device=dev)
+    mean_sq = torch.empty((B,), dtype=torch.float64, device=dev)
+    H.check(H.lib().dx_pitch_candidates(H.ptr(wavs), wavs.stride(0), H.ptr(n_samples), H.ptr(mean_sq), H.ptr(lags), H.ptr(vals),
+                                        B, S, A, step, window, lag_min, lag_max, H.stream()))
+    return lags, vals
+
+
+def pitch_track_batch(wavs, n_samples, hparams, sr=None):
+    ''' both kernels: (log_pitch (B, T) fp32, n_frames (B,) int64, hz (B, A) fp32 per analysis frame, (lags, values)) '''
+    lags, vals = pitch_candidates_batch(wavs, n_samples, hparams, sr)
+    sr, step, _, _, lag_max = pitch_geometry(hparams, sr)
+    B, S = wavs.shape
+    _, A, K = lags.shape
+    hop = int(hparams.hop_length)
+    T = 1 + S // hop
+    dev = wavs.device
+    back = torch.empty((B, A, K + 1), dtype=torch.uint8, device=dev)
+    hz = torch.empty((B, A), dtype=torch.float32, device=dev)
+    log_pitch = torch.empty((B, T), dtype=torch.float32, device=dev)
+    n_frames = torch.empty((B,), dtype=torch.int64, device=dev)
+    H.check(H.lib().dx_pitch_viterbi(H.ptr(lags), H.ptr(vals), H.ptr(n_samples), H.ptr(back), H.ptr(hz), H.ptr(log_pitch),
+                                     H.ptr(n_frames), B, S, A, T, sr, step, hop, lag_max, float(hparams.uv_cost), H.stream()))
+    return log_pitch, n_frames, hz, (lags, vals)
+
+
+def pitch_batch(wavs, n_samples, hparams, sr=None):
+    ''' wavs (B, S) float32 device tensor (right-padded), n_samples (B,) int64 device tensor, sampled at `sr` (default
+        hparams.sampling_rate).  Returns (log_pitch (B, T) fp32 on the device, n_frames (B,) int64): per mel frame
+        (T = 1 + S // hop_length, n_frames[b] = 1 + n_samples[b] // hop_length, as `mel_spectrogram_batch` with `centered`)
+        log(Hz), 0 where unvoiced and for frames >= n_frames[b].
+        hparams.f0_interval, min_f0, max_f0 and uv_cost mean what they mean to the reference's binary (analysis interval, search
+        range, weight of the unvoiced hypothesis).  hparams.uv_interval is accepted and ignored: it spaces REAPER's pitch marks
+        in unvoiced regions and has no meaning without pitch marks.  The Hz is not rounded to an integer, as the reference
+        binary's output format does. '''
+    log_pitch, n_frames, _, _ = pitch_track_batch(wavs, n_samples, hparams, sr)
+    return log_pitch, n_frames
+
+
+def extract_pitch(wav, fs, hparams, device='cuda:0'):
+    ''' reference signature (`extract_features.py:222`): wav (n,) in [-1, 1] sampled at fs -> (1 + n // hop_length,) NumPy,
+        log(Hz) per mel frame, 0 where unvoiced '''
+    w = torch.as_tensor(np.asarray(wav, dtype=np.float32)).reshape(1, -1).to(device)
+    n = torch.tensor([w.shape[1]], dtype=torch.int64, device=device)
+    log_pitch, nfr = pitch_batch(w, n, hparams, sr=fs)
+    return log_pitch[0, :int(nfr[0])].cpu().numpy()
 
 
 def extract_energy(mel_spec):

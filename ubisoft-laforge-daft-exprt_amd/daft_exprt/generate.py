@@ -4,7 +4,8 @@ Keeps the hot-path part of the reference driver (`src/daft_exprt/generate.py`): 
 per-symbol duration / energy / pitch control factors, reference `.npz` prosody, sort by symbol count, padding rules),
 `generate_batch_mel_specs` (242-317: one `model.inference` call per batch, crop per item, `.npz` with the same keys,
 Griffin-Lim preview `.wav` per item on the GPU, `daft_exprt/griffin_lim.py`) and `generate_mel_specs` (320-437: chunking +
-real-time-factor accounting).  Text phonemisation (MFA g2p) and plots are outside the accelerated path (SURVEY 2, rows
+real-time-factor accounting) and `extract_reference_parameters` (440-462: a reference recording -> the `.npz` of energy, pitch
+and mel-spectrogram the collate reads; wav reading, resampling, pitch and mel all on the GPU).  Text phonemisation (MFA g2p) and plots are outside the accelerated path (SURVEY 2, rows
 6/13/15): sentences arrive phonemised --
 a list of words (lists of phone symbols) and boundary symbols, exactly what `prepare_sentences_for_inference` returns.
 """
@@ -35,8 +36,8 @@ def _symbol_ids(sentence, hparams):
 
 def collate_tensors(batch_sentences, batch_dur_factors, batch_energy_factors, batch_pitch_factors, pitch_transform,
                     batch_refs, batch_speaker_ids, batch_file_names, hparams):
-    ''' same contract as `generate.py:140-239`; `batch_refs` are `.npz` paths (keys energy, pitch, mel_spec) or
-        already-loaded (energy, pitch, mel_spec) triples '''
+    ''' same contract as `generate.py:140-239`; `batch_refs` are `.npz` paths (keys energy, pitch, mel_spec),
+        already-loaded (energy, pitch, mel_spec) triples, or `.wav` paths whose parameters are extracted on the fly '''
     assert pitch_transform in ('add', 'multiply')
     neutral_pitch = 0. if pitch_transform == 'add' else 1.
     rows = []
@@ -49,7 +50,9 @@ def collate_tensors(batch_sentences, batch_dur_factors, batch_energy_factors, ba
         assert len(dur_f) == n, _logger.error(f'{len(dur_f)} duration factors whereas there a {n} symbols')
         assert len(en_f) == n, _logger.error(f'{len(en_f)} energy factors whereas there a {n} symbols')
         assert len(pi_f) == n, _logger.error(f'{len(pi_f)} pitch factors whereas there a {n} symbols')
-        if isinstance(ref, (str, os.PathLike)):
+        if _is_wav(ref):
+            ref = reference_parameters([ref], hparams)[0]
+        elif isinstance(ref, (str, os.PathLike)):
             data = np.load(ref)
             ref = (data['energy'], data['pitch'], data['mel_spec'])
         energy, pitch, mel = (torch.as_tensor(np.asarray(a)).float() for a in ref)
@@ -74,9 +77,16 @@ def collate_tensors(batch_sentences, batch_dur_factors, batch_energy_factors, ba
         ref_lengths, speaker_ids, file_names
 
 
+def _is_wav(ref):
+    return isinstance(ref, (str, os.PathLike)) and str(ref).lower().endswith('.wav')
+
+
 def _ref_name(ref, idx):
     ''' `_ref_<basename without .npz>` part of the output file name (`generate.py:250-251`); references handed over as
-        already-loaded triples (an extension, the reference only takes paths) are named by their position '''
+        already-loaded triples (an extension, the reference only takes paths) are named by their position, `.wav`
+        references (an extension too) by their basename without `.wav` '''
+    if _is_wav(ref):
+        return os.path.basename(str(ref))[:-len('.wav')]
     if isinstance(ref, (str, os.PathLike)):
         return os.path.basename(str(ref)).replace('.npz', '')
     return f'mem{idx}'
@@ -130,6 +140,88 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
             griffin_lim.write_wav(os.path.join(output_dir, f'{name}.wav'), hparams.sampling_rate, wavs[i, :int(n_samples[i])])
         _logger.warning('Mel-spec / alignment plots are outside the accelerated path')
     return predictions
+
+
+def _parameters_of(wavs, hparams, device):
+    ''' [(energy (T,), pitch (T,), mel_spec (n_mel, T)) NumPy] of float32 waveforms (a list) sampled at hparams.sampling_rate:
+        one `pitch_batch` and one `mel_spectrogram_batch` over the right-padded batch '''
+    from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
+    lengths = [int(w.shape[0]) for w in wavs]
+    x = torch.zeros((len(wavs), max(lengths)), dtype=torch.float32)
+    for i, w in enumerate(wavs):
+        x[i, :lengths[i]] = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+    x, n = x.to(device), torch.tensor(lengths, dtype=torch.int64, device=device)
+    pitch, n_pitch = pitch_batch(x, n, hparams)
+    mel, energy, n_mel = mel_spectrogram_batch(x, n, hparams)
+    pitch, energy, mel, n_pitch, n_mel = (t.cpu().numpy() for t in (pitch, energy, mel, n_pitch, n_mel))
+    out = []
+    for i in range(len(wavs)):
+        t = int(n_mel[i])
+        assert int(n_pitch[i]) == t, f'{int(n_pitch[i])} -- {t}'            # `generate.py:459`
+        out.append((energy[i, :t].copy(), pitch[i, :t].copy(), mel[i, :, :t].copy()))
+    return out
+
+
+def reference_parameters(audio_refs, hparams, device=None):
+    ''' [(energy, pitch, mel_spec)] of wav files, in order.  Files are read on the host (`audio.read_wav`), resampled to
+        hparams.sampling_rate on the device in one launch per source rate, then tracked and analysed as one batch. '''
+    from daft_exprt import _hip as H
+    from daft_exprt import audio
+    dev = H.device(device)
+    sr = int(hparams.sampling_rate)
+    loaded = []
+    for path in audio_refs:
+        y, rate = audio.read_wav(path)
+        loaded.append((audio.to_float_mono(y), rate))
+    wavs = [None] * len(loaded)
+    for rate in sorted({r for _, r in loaded}):
+        idx = [i for i, (_, r) in enumerate(loaded) if r == rate]
+        if rate == sr:
+            for i in idx:
+                wavs[i] = loaded[i][0]
+            continue
+        lengths = [loaded[i][0].shape[0] for i in idx]
+        x = torch.zeros((len(idx), max(lengths)), dtype=torch.float32)
+        for row, i in enumerate(idx):
+            x[row, :lengths[row]] = torch.from_numpy(loaded[i][0])
+        y, _ = audio.resample_batch(x.to(dev), torch.tensor(lengths, dtype=torch.int64, device=dev), rate, sr)
+        y = y.cpu().numpy()
+        for row, i in enumerate(idx):
+            wavs[i] = y[row, :audio.out_length(lengths[row], rate, sr)]
+    return _parameters_of(wavs, hparams, dev)
+
+
+def _ref_file(audio_ref, output_dir):
+    return os.path.join(output_dir, os.path.basename(audio_ref).replace('.wav', '') + '.npz')
+
+
+def extract_reference_parameters(audio_ref, output_dir, hparams, device=None):
+    ''' `generate.py:440-462`, same contract: `<output_dir>/<name of audio_ref without .wav>.npz` with keys `energy`, `pitch`
+        (log Hz per mel frame, 0 where unvoiced) and `mel_spec`, all of the same number of frames; nothing is done when the
+        file already exists.  Built from `audio.load_wav` (resampling on the device when the file's rate differs),
+        `pitch_batch` and `mel_spectrogram_batch`; the energy is the front-end's own (the norm of exp(mel) over the channels,
+        what `extract_energy(np.exp(mel_spec))` computes). '''
+    from daft_exprt import _hip as H
+    from daft_exprt import audio
+    os.makedirs(output_dir, exist_ok=True)
+    ref_file = _ref_file(audio_ref, output_dir)
+    if not os.path.isfile(ref_file):
+        dev = H.device(device)
+        wav, _ = audio.load_wav(audio_ref, sr=hparams.sampling_rate, device=dev)
+        energy, pitch, mel_spec = _parameters_of([wav], hparams, dev)[0]
+        np.savez(ref_file, energy=energy, pitch=pitch, mel_spec=mel_spec)
+
+
+def extract_reference_parameters_batch(audio_refs, output_dir, hparams, device=None):
+    ''' `extract_reference_parameters` for a whole style bank: the files that have no `.npz` yet go through one resampling
+        launch per source rate, one pitch track and one mel front-end call together '''
+    os.makedirs(output_dir, exist_ok=True)
+    todo = [ref for ref in audio_refs if not os.path.isfile(_ref_file(ref, output_dir))]
+    todo = list(dict.fromkeys(todo))
+    if not todo:
+        return
+    for ref, (energy, pitch, mel_spec) in zip(todo, reference_parameters(todo, hparams, device)):
+        np.savez(_ref_file(ref, output_dir), energy=energy, pitch=pitch, mel_spec=mel_spec)
 
 
 LAST_TIME_PERF = {}   # filled by generate_mel_specs(get_time_perf=True): what the reference only logs (generate.py:433-435)
