@@ -588,6 +588,37 @@ int dx_pitch_viterbi(const float* cand_lag, const float* cand_val, const int64_t
                      float* log_pitch, int64_t* n_frames, int B, long S, int A, int T, int sr, double step, int hop,
                      int lag_max, float uv_cost, void* stream);
 
+/* ---- K21: per-utterance glue of training-feature extraction (extract_features.py:387-494, one utterance per process there).
+ * Additive entry points.
+ *
+ * dx_wav_crop (replaces extract_features.py:426, `wav[int(sent_begin * fs): int(sent_end * fs)]`): x (B, ldx) fp32 with S <= ldx
+ * valid columns, crop (B, 2) int64 = (begin_b, len_b) -> y (B, ldy): y[b, s] = x[b, begin_b + s] for s < len_b, 0 for
+ * len_b <= s < ldy.  The mel front-end reflects at the edges of its row, so the crop becomes a row of its own.  Samples outside
+ * [0, S) read as 0.
+ *
+ * dx_marker_durations (replaces extract_features.py:69-111, `duration_to_integer(float_durations, hparams, nb_samples=len(wav))`,
+ * with its int() truncations and order of operations; K16 is the nb_samples=None form fed from predicted durations): spans
+ * (B, L, 2) fp64 = the aligner rows' (begin, end) in seconds relative to the sentence begin, n_rows (B) of them per utterance,
+ * n_samples (B) = length of the cropped waveform.  durations (B, L): the list the reference returns, left-aligned, zeros behind
+ * it (all zeros on status 1 / 2); n_out (B, may be NULL): its length.  Times in fp64, counting in integers.  status (B):
+ *   0 ok;  1 the reference raises IndexError (the rows run out before the frames do, or there is no frame at all);
+ *   2 it raises ValueError (a row of zero length is reached);
+ *   3 one of the asserts at extract_features.py:437-439 fails: the list is not n_rows long, or its sum is not the mel's frame
+ *     count (centered ? 1 + n / hop : 1 + (n - filter_length) / hop, 0 below one window), or it holds a 0.
+ *
+ * dx_symbol_pool (replaces extract_features.py:272-296 `get_symbols_pitch` and 307-327 `get_symbols_energy`): energy / log_pitch
+ * (B, ldt) fp32 with T <= ldt frames, durations (B, L) int64, n_rows (B).  Row l < n_rows[b] with duration d > 0 owns the next d
+ * frames; a row with d == 0 gives 0 and owns nothing.  sym_energy[b, l] = mean of the row's frames; sym_pitch[b, l] = mean of
+ * the row's frames that are > 0, 0 when there is none.  Sums in fp64 in an order fixed by the row alone, one rounding to fp32.
+ * Rows l >= n_rows[b] are written as 0.  The durations of an utterance must not add up to more than T (frames past T are not
+ * read). */
+int dx_wav_crop(const float* x, long ldx, const int64_t* crop, float* y, long ldy, int B, long S, void* stream);
+int dx_marker_durations(const double* spans, const int64_t* n_rows, const int64_t* n_samples, int64_t* durations, int64_t* n_out,
+                        int* status, int B, int L, double sampling_rate, int filter_length, int hop_length, int centered,
+                        void* stream);
+int dx_symbol_pool(const float* energy, const float* log_pitch, long ldt, const int64_t* durations, const int64_t* n_rows,
+                   float* sym_energy, float* sym_pitch, int B, int T, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

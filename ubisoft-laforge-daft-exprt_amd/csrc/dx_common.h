@@ -46,6 +46,16 @@ __host__ __device__ static inline int dx_fill_end(int len, int N) {
   return f < N ? f : N;
 }
 
+// ---- frames of a marker span (duration_to_integer, extract_features.py:83-95) -----------------------------------------------
+__host__ __device__ static inline long dx_floordiv(long a, long b) { long q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
+// how many of the frame centres half + hop * i, 0 <= i < nb_frames, fall in (sb, se] (sample indices); shared by the two forms of
+// duration_to_integer: K16 (spans accumulated from predicted durations) and K21 (spans read from aligner markers)
+__host__ __device__ static inline long dx_span_frames(long sb, long se, long half, long hop, long nb_frames) {
+  long lo = dx_floordiv(sb + 1 - half + hop - 1, hop); if (lo < 0) lo = 0;   // ceil((sb + 1 - half) / hop)
+  long hi = dx_floordiv(se - half, hop); if (hi > nb_frames - 1) hi = nb_frames - 1;
+  return hi - lo + 1 > 0 ? hi - lo + 1 : 0;
+}
+
 // ---- device helpers -------------------------------------------------------------------
 template <typename T>
 struct Vec8;

@@ -233,8 +233,6 @@ __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, long 
 }
 
 // ------------------------------------------------------------------ integer durations (model.py:789-812 + extract_features.py:69-111)
-__device__ __forceinline__ long floordiv(long a, long b) { long q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
-
 // fp64 + integer arithmetic in the reference's order of operations: the walk over the symbols is SERIAL by definition (a running fp64
 // sum whose rounding the integer frame counts depend on), so one lane per utterance does it -- but on a copy of the row in LDS: the
 // first version walked global memory, one dependent ~1 us round trip per symbol and loop (207 us for B = 256, L = 160: 2 % of a
@@ -265,9 +263,7 @@ __device__ __forceinline__ void int_durations_walk(DP d, OP o, int L, double sr,
     const double bg = end_prev, e = end_prev + (double)d[l];
     end_prev += (double)d[l];
     const long sb = (long)(bg * sr), se = (long)(e * sr);
-    long lo = floordiv(sb + 1 - half + hop - 1, hop); if (lo < 0) lo = 0;   // ceil((sb + 1 - half) / hop)
-    long hi = floordiv(se - half, hop); if (hi > nb_frames - 1) hi = nb_frames - 1;
-    const long n = hi - lo + 1 > 0 ? hi - lo + 1 : 0;
+    const long n = dx_span_frames(sb, se, half, hop, nb_frames);      // (dx_common.h, shared with K21)
     o[l] = n;
     assigned += n;
     if (first < 0) first = l;

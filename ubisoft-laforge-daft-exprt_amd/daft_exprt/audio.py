@@ -145,6 +145,33 @@ def ft_pack(mel, lengths, wavs, crop, mel_total, wav_total):
     return buf[:mel_bytes + 2 * int(wav_total)]
 
 
+def crop_range(sent_begin, sent_end, fs, n_samples):
+    ''' (begin, length) of `wav[int(sent_begin * fs): int(sent_end * fs)]` for a wav of n_samples (`fine_tune.py:100`,
+        `extract_features.py:426`), with Python's slice rules '''
+    r = range(int(n_samples))[int(sent_begin * fs): int(sent_end * fs)]
+    return (r.start, len(r)) if len(r) else (0, 0)
+
+
+def device_waves(utts, fs, device):
+    ''' utts: objects with `.samples` (mono float32 NumPy) and `.rate`.  Returns the (B, S) fp32 device waveforms at fs and
+        their lengths (host ints): one H2D copy and, for every source rate other than fs, one resample launch '''
+    n_total = [len(u.samples) if u.rate == fs else out_length(len(u.samples), u.rate, fs) for u in utts]
+    wavs = torch.zeros((len(utts), max(max(n_total), 1)), dtype=torch.float32, device=device)
+    for rate in sorted(set(u.rate for u in utts)):
+        rows = [b for b, u in enumerate(utts) if u.rate == rate]
+        n_in = [len(utts[b].samples) for b in rows]
+        host = torch.zeros((len(rows), max(max(n_in), 1)), dtype=torch.float32).pin_memory()
+        for i, b in enumerate(rows):
+            host[i, :n_in[i]] = torch.from_numpy(utts[b].samples)
+        x = host.to(device, non_blocking=True)
+        if rate != fs:
+            n_dev = torch.tensor(n_in, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+            x, _ = resample_batch(x, n_dev, rate, fs)
+        idx = torch.tensor(rows, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+        wavs[:, :x.shape[1]].index_copy_(0, idx, x)
+    return wavs, n_total
+
+
 # ---- WAV files ------------------------------------------------------------------------------------------------------------
 
 _KSDATAFORMAT_TAIL = b'\x00\x00\x00\x00\x10\x00\x80\x00\x00\xaa\x00\x38\x9b\x71'    # WAVE_FORMAT_EXTENSIBLE sub-format GUID tail

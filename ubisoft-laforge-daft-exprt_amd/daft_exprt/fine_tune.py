@@ -29,7 +29,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from daft_exprt.audio import ft_pack, out_length, read_wav, resample_batch, to_float_mono, write_wav_int16
+from daft_exprt.audio import crop_range, ft_pack, read_wav, to_float_mono, write_wav_int16
+from daft_exprt.audio import device_waves as _device_waves
 from daft_exprt.data_loader import prepare_data_loaders
 from daft_exprt.extract_features import nb_frames
 from daft_exprt.hparams import HyperParams
@@ -53,13 +54,6 @@ def markers_span(markers_file):
     return float(lines[0].strip().split(sep='\t')[0]), float(lines[-1].strip().split(sep='\t')[1])
 
 
-def crop_range(sent_begin, sent_end, fs, n_samples):
-    ''' (begin, length) of `wav[int(sent_begin * fs): int(sent_end * fs)]` for a wav of n_samples (`fine_tune.py:100`),
-        with Python's slice rules '''
-    r = range(int(n_samples))[int(sent_begin * fs): int(sent_end * fs)]
-    return (r.start, len(r)) if len(r) else (0, 0)
-
-
 class _Utterance(object):
     def __init__(self, feature_dir, feature_file, speaker, samples, rate, span):
         self.feature_dir, self.feature_file, self.speaker = feature_dir, feature_file, speaker
@@ -76,26 +70,6 @@ def _read_batch(hparams, feature_dirs, feature_files):
         span = markers_span(os.path.join(root, 'align', f'{feature_file}.markers'))
         out.append(_Utterance(feature_dir, feature_file, speaker, to_float_mono(x), rate, span))
     return out
-
-
-def _device_waves(utts, fs, device):
-    ''' (B, S) fp32 device waveforms at fs and their lengths (host ints): one H2D copy and, for every source rate other than
-        fs, one resample launch '''
-    n_total = [len(u.samples) if u.rate == fs else out_length(len(u.samples), u.rate, fs) for u in utts]
-    wavs = torch.zeros((len(utts), max(max(n_total), 1)), dtype=torch.float32, device=device)
-    for rate in sorted(set(u.rate for u in utts)):
-        rows = [b for b, u in enumerate(utts) if u.rate == rate]
-        n_in = [len(utts[b].samples) for b in rows]
-        host = torch.zeros((len(rows), max(max(n_in), 1)), dtype=torch.float32).pin_memory()
-        for i, b in enumerate(rows):
-            host[i, :n_in[i]] = torch.from_numpy(utts[b].samples)
-        x = host.to(device, non_blocking=True)
-        if rate != fs:
-            n_dev = torch.tensor(n_in, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
-            x, _ = resample_batch(x, n_dev, rate, fs)
-        idx = torch.tensor(rows, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
-        wavs[:, :x.shape[1]].index_copy_(0, idx, x)
-    return wavs, n_total
 
 
 class _Writer(object):
