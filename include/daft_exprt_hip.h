@@ -619,6 +619,28 @@ int dx_marker_durations(const double* spans, const int64_t* n_rows, const int64_
 int dx_symbol_pool(const float* energy, const float* log_pitch, long ldt, const int64_t* durations, const int64_t* n_rows,
                    float* sym_energy, float* sym_pitch, int B, int T, int L, void* stream);
 
+/* ---- K22: the prosody-transfer metric (scripts/evaluation/compare_pitch_curves.py:5-45, `pcc_on_2_pitch_curve` with `_remove_unvoiced`,
+ * `scipy.signal.resample` and `_pcc`).  Additive entry points.
+ *
+ * dx_curve_pcc: ref (B, ld_ref) fp32 with n_ref[b] <= T_ref values per row, dut (B, ld_dut) fp32 with n_dut[b] <= T_dut; nothing at or
+ * past n_ref[b] / n_dut[b] is read.  Per row, independently of the other rows:
+ *   1. with remove_unvoiced the values > 0 of each curve are kept, in order (NaN and values <= 0 count as unvoiced); without it all
+ *      n values.  kept_ref[b] = num, kept_dut[b] = Nx: the lengths left.
+ *   2. the kept dut is resampled to num values as scipy.signal.resample does for real input: with N = min(num, Nx),
+ *        X[k] = sum_n x[n] e^{-2 pi i k n / Nx}, k = 0 .. N / 2;     y[m] = 1 / Nx * sum_k w_k Re(X[k] e^{+2 pi i k m / num}),
+ *      w_0 = 1, w_k = 2, and for the bin N / 2 of an even N w = 2 when num < Nx and w = 1 when num >= Nx.  Direct sums in fp32 over
+ *      the curve centred on its mean (added back to y); the angle index k n mod N is advanced in integers and looked up in a table
+ *      computed in double.  resampled (B, ld_rs), ld_rs >= T_ref, may be NULL: y in [0, num), the rest of the row is not written.
+ *   3. pcc[b] = mean((ref - mean ref) (y - mean y)) / (std ref * std y), means first, then the centred sums, in double.
+ *   4. pcc[b] = NaN when num = 0 or Nx = 0 (the reference returns NaN for an empty ref and raises ValueError for an empty dut; NaN
+ *      for both is an extension) or when a standard deviation is 0; `resampled` is NaN in [0, num) when Nx = 0.
+ * One workgroup per row with both curves, one twiddle table and the spectrum in LDS: T_ref, T_dut > dx_curve_pcc_max_len() = 4096
+ * (81 984 B of LDS, one workgroup per CU; 47 s of frames at hop 256, 22.05 kHz) returns DX_ERR_UNSUPPORTED before any launch. */
+long dx_curve_pcc_max_len(void);
+int dx_curve_pcc(const float* ref, long ld_ref, const int64_t* n_ref, const float* dut, long ld_dut, const int64_t* n_dut,
+                 float* pcc, int* kept_ref, int* kept_dut, float* resampled, long ld_rs, int B, int T_ref, int T_dut,
+                 int remove_unvoiced, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,159 @@
+#!/usr/bin/env python
+"""Batched prosody-transfer synthesis with objective scores, behind the flags of the reference's `scripts/synthesize.py`:
+    python scripts/synthesize.py -out OUT_DIR -chk CHECKPOINT -tf SENTENCES -sb STYLE_BANK [-bs N] [-rtf] [-ctrl]
+
+  -tf   phonemised sentences, one `file_name|{P1 P2} {P3} , {P4} ? ~` per line: the `sentences_to_generate.txt` the reference
+        writes after text cleaning and MFA g2p, which stay outside this project (`generate.read_phonemised_sentences`)
+  -sb   directory of reference `.wav` files; each gets its `.npz` of energy, pitch and mel-spectrogram beside it, extracted on
+        the GPU as one batch
+  -rtf  an extra pass without audio that logs the real-time factor at this batch size
+  -ctrl the reference's control example instead of plain transfer: every symbol 1.25 times longer, pitch shifted by +50 Hz
+
+Every sentence gets a random reference of the style bank and a random speaker (`random.seed(1234)`), is synthesised with
+Griffin-Lim preview audio and scored on the device against its reference: `<out>/prosody_transfer.json` holds, per output file,
+the pitch and energy correlation (`daft_exprt/evaluate.py`; null where undefined) and the frame counts, and a summary with the
+mean and median of the defined values and the number of undefined ones.  Without -ctrl each preview is renamed to
+`<idx>_<name>.wav` and a copy of its reference recording is put beside it as `<idx>_ref.wav`, so that the two sort together."""
+import argparse
+import json
+import logging
+import math
+import os
+import random
+import shutil
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'ubisoft-laforge-daft-exprt_amd')
+sys.path.insert(0, PKG)
+
+from daft_exprt import generate  # noqa: E402
+from daft_exprt.hparams import HyperParams  # noqa: E402
+from daft_exprt.model import DaftExprt  # noqa: E402
+
+_logger = logging.getLogger('synthesize')
+CONTROL = {'duration': 1.25, 'pitch': 50.0, 'pitch_transform': 'add'}      # the -ctrl example: slower, and 50 Hz higher
+METRICS = ('pitch_pcc', 'energy_pcc')
+
+
+def load_model(checkpoint):
+    ''' (model on cuda:0, the hyper-parameters stored in the checkpoint); `module.` prefixes of data-parallel training are dropped '''
+    ckpt = torch.load(checkpoint, map_location='cuda:0', weights_only=False)
+    hparams = HyperParams(verbose=False, **ckpt['config_params'])
+    weights = {(name[len('module.'):] if name.startswith('module.') else name): t for name, t in ckpt['state_dict'].items()}
+    torch.cuda.set_device(0)
+    model = DaftExprt(hparams).cuda(0)
+    model.load_state_dict(weights)
+    return model, hparams
+
+
+def style_bank(directory, hparams):
+    ''' the `.npz` prosody files of the bank, sorted; missing ones are extracted from their `.wav` in one batch '''
+    recordings = sorted(f for f in os.listdir(directory) if f.endswith('.wav'))
+    generate.extract_reference_parameters_batch([os.path.join(directory, f) for f in recordings], directory, hparams)
+    bank = sorted(os.path.join(directory, f) for f in os.listdir(directory) if f.endswith('.npz'))
+    if not bank:
+        raise SystemExit(f'{directory}: no reference recording (.wav) or prosody file (.npz)')
+    return bank
+
+
+def n_symbols(sentence):
+    return sum(len(item) if isinstance(item, (list, tuple)) else 1 for item in sentence)
+
+
+def run(args, model, hparams, control=None, audio=True, scores=None):
+    ''' one pass over the sentence file; returns [(sentence index, output name, reference .npz)] in sentence order '''
+    sentences, names = generate.read_phonemised_sentences(args.text_file, hparams.symbols)
+    bank = style_bank(args.style_bank, hparams)
+    refs = [random.choice(bank) for _ in sentences]
+    speakers = [random.choice(hparams.speakers_id) for _ in sentences]
+    dur = pitch = None
+    if control is not None:
+        dur = [[control['duration']] * n_symbols(s) for s in sentences]
+        pitch = [control['pitch_transform'], [[control['pitch']] * n_symbols(s) for s in sentences]]
+    os.makedirs(args.output_dir, exist_ok=True)
+    predictions = generate.generate_mel_specs(model, sentences, list(names), speakers, refs, args.output_dir, hparams, dur_factors=dur,
+                                              pitch_factors=pitch, batch_size=args.batch_size, use_griffin_lim=audio,
+                                              get_time_perf=not audio, scores=scores)
+    outputs = []
+    for idx, name in enumerate(names):      # the driver returns its own names, a batch at a time in order of length
+        mine = [key for key in predictions if key.startswith(f'{name}_spk_{speakers[idx]}_ref_')]
+        if len(mine) != 1:
+            raise RuntimeError(f'sentence {idx} ("{name}"): expected one output, found {mine}')
+        outputs.append((idx, mine[0], refs[idx]))
+    return outputs
+
+
+def pair_with_references(args, outputs):
+    ''' {output name: paired name}: `<idx>_<output name>.wav` next to `<idx>_ref.wav`, a copy of the reference recording '''
+    paired = {}
+    for idx, name, ref in outputs:
+        preview = os.path.join(args.output_dir, f'{name}.wav')
+        recording = os.path.splitext(ref)[0] + '.wav'
+        for path in (preview, recording):
+            if not os.path.isfile(path):
+                raise FileNotFoundError(path)
+        paired[name] = f'{idx}_{name}'
+        os.replace(preview, os.path.join(args.output_dir, f'{paired[name]}.wav'))
+        shutil.copyfile(recording, os.path.join(args.output_dir, f'{idx}_ref.wav'))
+    return paired
+
+
+def summarise(entries):
+    ''' mean and median of the defined values of each correlation, and how many are undefined '''
+    summary = {'files': len(entries)}
+    for key in METRICS:
+        values = [e[key] for e in entries.values() if e[key] is not None]
+        summary[key] = {'mean': statistics.fmean(values) if values else None, 'median': statistics.median(values) if values else None,
+                        'undefined': len(entries) - len(values)}
+    return summary
+
+
+def write_scores(args, scores, wav_names):
+    ''' `<out>/prosody_transfer.json`: {'files': {name: scores + 'wav'}, 'summary': ...}; NaN is written as null '''
+    entries = {}
+    for name, values in scores.items():
+        entry = {k: (None if isinstance(v, float) and math.isnan(v) else v) for k, v in values.items()}
+        entry['wav'] = f'{wav_names.get(name, name)}.wav'
+        entries[name] = entry
+    report = {'files': entries, 'summary': summarise(entries)}
+    path = os.path.join(args.output_dir, 'prosody_transfer.json')
+    with open(path, 'w', encoding='utf-8') as f:
+        json.dump(report, f, indent=1)
+    for key in METRICS:
+        s = report['summary'][key]
+        if s['mean'] is None:
+            _logger.info(f'{key}: undefined for all {len(entries)} files')
+        else:
+            _logger.info(f'{key}: mean {s["mean"]:.3f}, median {s["median"]:.3f} over {len(entries) - s["undefined"]} files '
+                         f'({s["undefined"]} undefined)')
+    _logger.info(f'Prosody-transfer scores written to {path}')
+    return report
+
+
+def main():
+    parser = argparse.ArgumentParser(description='Synthesise phonemised sentences with prosody transferred from a style bank, and score the transfer')
+    parser.add_argument('-out', '--output_dir', required=True, help='where the .npz, .wav and prosody_transfer.json go')
+    parser.add_argument('-chk', '--checkpoint', required=True, help='training checkpoint (weights and hyper-parameters)')
+    parser.add_argument('-tf', '--text_file', required=True, help='phonemised sentences: file_name|{P1 P2} {P3} , {P4} ? ~ per line')
+    parser.add_argument('-sb', '--style_bank', required=True, help='directory of reference recordings (.wav)')
+    parser.add_argument('-bs', '--batch_size', type=int, default=50, help='sentences per inference call')
+    parser.add_argument('-rtf', '--real_time_factor', action='store_true', help='first time a pass without audio and log its real-time factor')
+    parser.add_argument('-ctrl', '--control', action='store_true', help='apply the duration x 1.25, pitch + 50 Hz example to every symbol')
+    args = parser.parse_args()
+    logging.basicConfig(format='%(asctime)s [%(levelname)s] %(message)s', datefmt='%Y-%m-%d %H:%M:%S', level=logging.INFO)
+    random.seed(1234)
+
+    model, hparams = load_model(args.checkpoint)
+    if args.real_time_factor:
+        run(args, model, hparams, audio=False)
+    scores = {}
+    outputs = run(args, model, hparams, control=CONTROL if args.control else None, scores=scores)
+    write_scores(args, scores, {} if args.control else pair_with_references(args, outputs))
+
+
+if __name__ == '__main__':
+    main()

@@ -94,7 +94,7 @@ def _ref_name(ref, idx):
 
 def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_factors, batch_energy_factors, batch_pitch_factors,
                              pitch_transform, batch_speaker_ids, batch_file_names, output_dir, hparams, n_jobs=1,
-                             use_griffin_lim=True):
+                             use_griffin_lim=True, scores=None):
     ''' `generate.py:242-317`, same contract: every file name gets the `_spk_<id>_ref_<reference>` suffix IN PLACE
         (the caller's list is updated like the reference does, 248-253), one `model.inference` call on the collated
         batch, `<output_dir>/<file_name>.npz` holding `mel_spec` (298), and the return value
@@ -102,7 +102,13 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         With `use_griffin_lim` (303-307, 110-137) the preview audio is made on the device from the decoder's mel before the
         copy to the host (`griffin_lim.griffin_lim_batch`, 30 iterations, device noise seeded with 0) and written as
         `<output_dir>/<file_name>.wav`: mono, `hparams.sampling_rate`, 64-bit float, peak 1.  Plots stay outside the
-        accelerated path. '''
+        accelerated path.
+        `scores` (an extension; needs `use_griffin_lim`): a dict that receives, per file name, the prosody-transfer scores of
+        the preview audio against its reference (`evaluate.prosody_transfer_scores`, computed on the device beside the audio):
+        `pitch_pcc`, `energy_pcc` (floats, NaN where undefined), `voiced_ref`, `voiced_gen`, `frames_ref`, `frames_gen` (ints).
+        With None nothing is computed and nothing else changes. '''
+    if scores is not None and not use_griffin_lim:
+        raise ValueError('scores are computed from the Griffin-Lim preview audio: pass use_griffin_lim=True')
     for idx, file_name in enumerate(batch_file_names):
         file_name += f'_spk_{batch_speaker_ids[idx]}'
         file_name += f'_ref_{_ref_name(batch_refs[idx], idx)}'
@@ -124,6 +130,9 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
     if use_griffin_lim:
         from daft_exprt import griffin_lim
         wavs, n_samples = griffin_lim.griffin_lim_batch(decoder_preds[0].float().contiguous(), decoder_preds[1], hparams)
+        if scores is not None:
+            from daft_exprt import evaluate
+            batch_scores = evaluate.prosody_transfer_scores(wavs, n_samples, inputs[6], inputs[5], inputs[8], hparams)
     duration, duration_int, energy, pitch, input_lengths = (t.detach().cpu().numpy() for t in encoder_preds)
     mel_spec, output_lengths = (t.detach().cpu().numpy() for t in decoder_preds)
     weights = alignments.detach().cpu().numpy()
@@ -138,6 +147,10 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         wavs, n_samples = wavs.cpu().numpy(), n_samples.cpu().numpy()
         for i, name in enumerate(file_names):
             griffin_lim.write_wav(os.path.join(output_dir, f'{name}.wav'), hparams.sampling_rate, wavs[i, :int(n_samples[i])])
+        if scores is not None:
+            host = {key: t.cpu().tolist() for key, t in batch_scores.items()}
+            for i, name in enumerate(file_names):
+                scores[name] = {key: host[key][i] for key in evaluate.SCORE_KEYS}
         _logger.warning('Mel-spec / alignment plots are outside the accelerated path')
     return predictions
 
@@ -224,17 +237,62 @@ def extract_reference_parameters_batch(audio_refs, output_dir, hparams, device=N
         np.savez(_ref_file(ref, output_dir), energy=energy, pitch=pitch, mel_spec=mel_spec)
 
 
+def read_phonemised_sentences(path, symbols=None):
+    ''' (sentences, file_names) of a file in the format `prepare_sentences_for_inference` writes (`generate.py:483-492`,
+        `sentences_to_generate.txt`): one `file_name|{P1 P2} {P3} , {P4} ? ~` per line.  A brace group is a word (a list of
+        phones), a bare token a boundary symbol, two adjacent words are separated by the whitespace symbol the writer's
+        whitespace collapse swallowed, a trailing `~` is the eos.  `symbols`: the table every phone and boundary must be in
+        (default: the English one); anything else raises ValueError naming the line. '''
+    import re
+    from daft_exprt.symbols import symbols_english, whitespace
+    table = set(symbols_english if symbols is None else symbols)
+    sentences, file_names = [], []
+    with open(path, 'r', encoding='utf-8') as f:
+        lines = [line.strip() for line in f]
+    for number, line in enumerate(lines, 1):
+        if not line:
+            continue
+        where = f'{path}, line {number}'
+        if '|' not in line:
+            raise ValueError(f'{where}: expected "file_name|phonemised sentence", got "{line}"')
+        file_name, text = line.split('|', 1)
+        if re.sub(r'\{[^{}]*\}', '', text).count('{') or re.sub(r'\{[^{}]*\}', '', text).count('}'):
+            raise ValueError(f'{where}: unbalanced braces in "{text}"')
+        sentence = []
+        for group, token in re.findall(r'\{([^{}]*)\}|(\S+)', text):
+            if token:
+                if token not in table:
+                    raise ValueError(f'{where}: unknown symbol "{token}"')
+                sentence.append(token)
+                continue
+            phones = group.split()
+            unknown = [phone for phone in phones if phone not in table]
+            if unknown or not phones:
+                raise ValueError(f'{where}: unknown symbol "{unknown[0]}"' if unknown else f'{where}: empty word')
+            if sentence and isinstance(sentence[-1], list):
+                sentence.append(whitespace)
+            sentence.append(phones)
+        if not sentence:
+            raise ValueError(f'{where}: no symbols')
+        sentences.append(sentence)
+        file_names.append(file_name)
+    return sentences, file_names
+
+
 LAST_TIME_PERF = {}   # filled by generate_mel_specs(get_time_perf=True): what the reference only logs (generate.py:433-435)
 
 
 def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_dir, hparams, dur_factors=None,
                        energy_factors=None, pitch_factors=None, batch_size=1, n_jobs=1, use_griffin_lim=False,
-                       get_time_perf=False):
+                       get_time_perf=False, scores=None):
     ''' `generate.py:320-437`, same contract: `pitch_factors = [transform, [per-sentence factor lists]]`, the list-length
         asserts, eval mode + no grad, chunks of `batch_size`, returns the predictions dict only.  With `get_time_perf`
         the real-time factor is logged exactly like the reference: wall time of the whole per-batch function (collate,
         H2D, inference, D2H, file writes) against `((n_frames - 1) * hop + n_fft - 2 * (n_fft // 2)) / sr` seconds of
-        audio per sentence (413-435); the numbers are also left in `LAST_TIME_PERF`. '''
+        audio per sentence (413-435); the numbers are also left in `LAST_TIME_PERF`.  `scores`: see
+        `generate_batch_mel_specs`. '''
+    if scores is not None and not use_griffin_lim:
+        raise ValueError('scores are computed from the Griffin-Lim preview audio: pass use_griffin_lim=True')
     n = len(sentences)
     dur_factors = [None for _ in range(n)] if dur_factors is None else dur_factors
     energy_factors = [None for _ in range(n)] if energy_factors is None else energy_factors
@@ -255,7 +313,7 @@ def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_d
             b_sent, b_refs, b_dur, b_en, b_pi, b_spk, b_names = chunk
             begin = time.time() if get_time_perf else None
             predictions.update(generate_batch_mel_specs(model, b_sent, b_refs, b_dur, b_en, b_pi, pitch_transform, b_spk,
-                                                        b_names, output_dir, hparams, n_jobs, use_griffin_lim))
+                                                        b_names, output_dir, hparams, n_jobs, use_griffin_lim, scores))
             time_per_batch += [time.time() - begin] if get_time_perf else []
     if get_time_perf:
         durations = []
