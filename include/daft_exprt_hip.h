@@ -641,6 +641,37 @@ int dx_curve_pcc(const float* ref, long ld_ref, const int64_t* n_ref, const floa
                  float* pcc, int* kept_ref, int* kept_dut, float* resampled, long ld_rs, int B, int T_ref, int T_dut,
                  int remove_unvoiced, void* stream);
 
+/* ---- K23: the numbers behind the validation figures (logger.py:34-157), reduced on the device.  Additive entry points.
+ *
+ * dx_film_hist_range / dx_film_hist_count (replace `histogram_plot(..., bins=50)` over the FiLM tensors, logger.py:100-126 through
+ * utils.py:18-36, i.e. numpy.histogram per block of gammas and of betas): film (rows, nb_blocks, width) fp32, rows = the utterances
+ * of the validation set; the first width / 2 values of a block are its gammas, the rest its betas (logger.py:118-125).  Group
+ * g = 2 * block + (0 gammas | 1 betas) holds rows * width / 2 values; G = 2 * nb_blocks groups.
+ *   range: minmax (G, 2) fp32 = the group's (min, max), finite (G) int = 1 when every value of the group is finite; a group with a
+ *          NaN or an infinity gets finite = 0 and minmax = (0, 0) (numpy raises there; a diagnostic must not stop a training run).
+ *   count: edges (G, 51) fp64, ascending, built by the HOST from minmax as numpy.histogram does (numpy.linspace(lo, hi, 51) in
+ *          double, lo - 0.5 .. hi + 0.5 when lo == hi); counts (G, 50) int64, cleared here.  Value x counts in bin i with
+ *          edges[i] <= x < edges[i + 1], the last bin closed, values outside the table in none; the comparison runs in double
+ *          against the table (an fp32 estimate only seeds the search), the counts are integer atomics: the result depends on
+ *          neither the launch geometry nor any rounding and equals numpy.histogram(values as float64, bins=50)[0].  Groups with
+ *          finite = 0 keep zero counts.
+ *
+ * dx_alignment_score (new; the numeric content of the "alignments" figure, logger.py:81-98 and 154-157): weights (B, L, T) fp32 as
+ * dx_gu_upsample_fwd returns them, durations_int (B, L) int64, in_lengths / out_lengths (B) int64.  Symbol l < in_lengths[b] owns
+ * the frames [c_l, c_l + d_l), c_l = sum_{j < l} d_j (exact integers), cut at out_lengths[b]; symbols at or past in_lengths[b]
+ * own nothing.  Per utterance:
+ *   frames[b] = min(sum_l d_l, out_lengths[b]), the owned frames;
+ *   hits[b]   = the owned frames t whose argmax_{l < in_lengths[b]} weights[b, l, t] is the owner (lowest l among equal maxima);
+ *   mass[b]   = the mean over the owned frames of weights[b, owner(t), t], summed in double, 0 when frames[b] == 0.
+ * The target alignment comes from the batch's own durations_int -- the integers the upsampler was teacher-forced with -- where the
+ * reference's figure re-derives integers from the FLOAT duration targets through duration_to_integer (logger.py:81-91): the score
+ * compares the alignment with what actually drove it.  L > 8192: DX_ERR_UNSUPPORTED (one utterance's prefix sums live in LDS). */
+int dx_film_hist_range(const float* film, float* minmax, int* finite, long rows, int nb_blocks, int width, void* stream);
+int dx_film_hist_count(const float* film, const double* edges, const int* finite, int64_t* counts, long rows, int nb_blocks,
+                       int width, void* stream);
+int dx_alignment_score(const float* weights, const int64_t* durations_int, const int64_t* in_lengths, const int64_t* out_lengths,
+                       int64_t* frames, int64_t* hits, float* mass, int B, int L, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -875,3 +875,42 @@ def prosody_control(energy, pitch, energy_factors, pitch_factors, durations_int,
     H.check(H.lib().dx_prosody_control(H.ptr(energy), H.ptr(pitch), H.ptr(energy_factors), H.ptr(pitch_factors),
                                        H.ptr(durations_int), H.ptr(speaker_ids), H.ptr(spk_mean), H.ptr(spk_std), int(mode),
                                        B, L, H.stream()))
+
+
+# ----------------------------------------------------------------------------- validation report
+FILM_BINS = 50
+
+
+def film_hist_range(film):
+    ''' film (rows, nb_blocks, width) fp32 -> (minmax (2 nb_blocks, 2) fp32, finite (2 nb_blocks,) int32); group 2 block + (0 gammas | 1 betas) '''
+    rows, nb, width = film.shape
+    assert film.is_contiguous() and film.dtype == torch.float32
+    minmax = _empty((2 * nb, 2), dtype=torch.float32, device=film.device)
+    finite = _empty((2 * nb,), dtype=torch.int32, device=film.device)
+    H.check(H.lib().dx_film_hist_range(H.ptr(film), H.ptr(minmax), H.ptr(finite), rows, nb, width, H.stream()))
+    return minmax, finite
+
+
+def film_hist_count(film, edges, finite):
+    ''' edges (2 nb_blocks, 51) fp64 on the device -> counts (2 nb_blocks, 50) int64 '''
+    rows, nb, width = film.shape
+    assert film.is_contiguous() and film.dtype == torch.float32
+    assert edges.is_contiguous() and edges.dtype == torch.float64 and tuple(edges.shape) == (2 * nb, FILM_BINS + 1)
+    counts = _empty((2 * nb, FILM_BINS), dtype=torch.int64, device=film.device)
+    H.check(H.lib().dx_film_hist_count(H.ptr(film), H.ptr(edges), H.ptr(finite), H.ptr(counts), rows, nb, width, H.stream()))
+    return counts
+
+
+def alignment_score(weights, durations_int, in_lengths, out_lengths):
+    ''' weights (B, L, T) fp32, durations_int (B, L) int64 -> (frames (B,) int64, hits (B,) int64, mass (B,) fp32) '''
+    B, L, T = weights.shape
+    assert weights.is_contiguous() and weights.dtype == torch.float32
+    assert durations_int.is_contiguous() and durations_int.dtype == torch.int64 and tuple(durations_int.shape) == (B, L)
+    assert in_lengths.dtype == torch.int64 and out_lengths.dtype == torch.int64 and in_lengths.numel() == B and out_lengths.numel() == B
+    dev = weights.device
+    frames = _empty((B,), dtype=torch.int64, device=dev)
+    hits = _empty((B,), dtype=torch.int64, device=dev)
+    mass = _empty((B,), dtype=torch.float32, device=dev)
+    H.check(H.lib().dx_alignment_score(H.ptr(weights), H.ptr(durations_int), H.ptr(in_lengths), H.ptr(out_lengths), H.ptr(frames),
+                                       H.ptr(hits), H.ptr(mass), B, L, T, H.stream()))
+    return frames, hits, mass

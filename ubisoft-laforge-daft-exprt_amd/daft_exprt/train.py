@@ -15,14 +15,18 @@ Step loop = `train.py:368-401, 475-494` with the device work restructured for MI
     8 `.item()` syncs per micro-batch, `loss.py:102-104`, `train.py:382`) costs no device idle time;
   * no per-iteration `dist.barrier()` (the reference's only paces log output, and its rank-local NaN test in front of it can
     deadlock): the gradient all-reduce keeps the ranks in step; validation and checkpoints keep their barriers.
-Validation scoring and the best-model checkpoint (`train.py:427-456`) are kept; validation figures and the
-benchmark-sentence synthesis (MFA, librosa, Griffin-Lim) are outside the accelerated path.
+Validation scoring and the best-model checkpoint (`train.py:427-456`) are kept.  What the reference draws into TensorBoard at
+every validation (`logger.py:34-157`) is written as data by `validation_report.ValidationReport`, reduced on the device batch
+by batch; the benchmark sentences are synthesised with Griffin-Lim audio at every checkpoint (`generate_benchmark_sentences`,
+`train.py:154-190`) from an already phonemised sentence file (no aligner runs here).
 """
 import argparse
 import json
 import logging
 import math
 import os
+import random
+import shutil
 import time
 
 import torch
@@ -36,6 +40,7 @@ from daft_exprt.model import DaftExprt
 from daft_exprt import config, ops, streams
 from daft_exprt.optim import FusedAdam
 from daft_exprt.parallel import GradReducer
+from daft_exprt.validation_report import ValidationReport
 
 _logger = logging.getLogger(__name__)
 FEATURES_HPARAMS = ['centered', 'cutoff', 'f0_interval', 'filter_length', 'hop_length', 'language', 'mel_fmax', 'mel_fmin',
@@ -392,17 +397,66 @@ class CapturedStep(object):
         return ent
 
 
-def validate(gpu, model, criterion, val_loader, hparams):
+def generate_benchmark_sentences(model, hparams, output_dir, iteration):
+    ''' `train.py:154-190`: the benchmark sentences in the voice of a random speaker id with the prosody of a random validation
+        utterance, mel-spectrograms and Griffin-Lim audio into `output_dir`, the reference wav copied next to them.  Both draws
+        come from `random.Random(hparams.seed + iteration)`.  The sentences are read from
+        `<benchmark_dir>/<language>/sentences_phonemised.txt` (the format of `generate.read_phonemised_sentences`): the
+        reference phonemises its plain `sentences.txt` with an aligner that does not run here.  When that file, the validation
+        list or the reference wav is missing, one line is logged and nothing is generated.  Returns the predictions or None. '''
+    from daft_exprt.generate import extract_reference_parameters, generate_mel_specs, read_phonemised_sentences
+    bench = getattr(hparams, 'benchmark_dir', None)
+    text_file = os.path.join(str(bench), str(hparams.language), 'sentences_phonemised.txt') if bench else ''
+    if not os.path.isfile(text_file):
+        _logger.info(f'No benchmark sentences generated: "{text_file or "hparams.benchmark_dir"}" does not exist')
+        return None
+    if not os.path.isfile(str(hparams.validation_files)):
+        _logger.info(f'No benchmark sentences generated: validation list "{hparams.validation_files}" does not exist')
+        return None
+    rng = random.Random(int(hparams.seed) + int(iteration))
+    speaker_id = rng.choice(list(hparams.speakers_id))
+    with open(hparams.validation_files, 'r', encoding='utf-8') as f:
+        references = [line.strip().split('|') for line in f if line.strip()]
+    reference = rng.choice(references) if references else None
+    audio_ref = ''
+    if reference is not None and len(reference) >= 2:
+        names = [speaker for speaker in hparams.speakers if reference[0].endswith(speaker)]
+        if names:
+            audio_ref = os.path.join(str(getattr(hparams, 'data_set_dir', '')), names[0], 'wavs', f'{reference[1]}.wav')
+    if not os.path.isfile(audio_ref):
+        _logger.info(f'No benchmark sentences generated: reference wav "{audio_ref}" does not exist')
+        return None
+    _logger.info(f'Generating benchmark sentences with speaker_id = {speaker_id}, audio_ref = {audio_ref}')
+    sentences, file_names = read_phonemised_sentences(text_file, hparams.symbols)
+    was_training = model.training
+    try:
+        extract_reference_parameters(audio_ref, output_dir, hparams, device=model.flat_parameters().device)
+        file_name = os.path.basename(audio_ref).replace('.wav', '')
+        refs = [os.path.join(output_dir, f'{file_name}.npz') for _ in sentences]
+        predictions = generate_mel_specs(model, sentences, file_names, [speaker_id for _ in sentences], refs, output_dir, hparams,
+                                         use_griffin_lim=True)
+        shutil.copyfile(audio_ref, os.path.join(output_dir, f'{file_name}.wav'))
+    finally:
+        model.train(was_training)     # generate_mel_specs leaves the model in eval mode
+    return predictions
+
+
+def validate(gpu, model, criterion, val_loader, hparams, report=None):
     ''' `train.py:193-233`: eval mode, no grad, criterion at iteration 0 (adversarial weight 0), batch
-        means of the total and of the five reconstruction terms.  Returns (val_loss, val_indiv_loss); the per-batch
-        targets / outputs the reference also returns only feed its TensorBoard figures (out of scope). '''
+        means of the total and of the five reconstruction terms.  Returns (val_loss, val_indiv_loss).  The per-batch targets /
+        outputs the reference also returns feed its TensorBoard figures: here a `ValidationReport` passed as `report` is handed
+        every batch while it is on the device and keeps what those figures need; without one nothing else happens. '''
     val_loss, n = 0., 0
     indiv = {k: 0. for k in KEYS[2:]}
     model.eval()
     with torch.no_grad():
         for batch in val_loader:
             inputs, targets, _ = model.parse_batch(gpu, batch)
-            loss, terms = criterion(model(inputs), targets, iteration=0)
+            outputs = model(inputs)
+            # (fixed_order: the loss terms of the same outputs are the same bits on every call, with or without a report beside them)
+            loss, terms = criterion(outputs, targets, iteration=0, fixed_order=True)
+            if report is not None:
+                report.add_batch(inputs, targets, outputs)
             val_loss += float(loss)
             for k in indiv:
                 indiv[k] += terms[k]
@@ -577,7 +631,9 @@ def train(gpu, hparams, log_file):
             # ---- model evaluation (`train.py:427-456`): every rank scores the whole validation set, rank 0 keeps the best
             if val_loader is not None and iteration % hparams.iters_check_for_model_improvement == 0:
                 _logger.info('Validating....')
-                val_loss, val_indiv = validate(gpu, model, criterion, val_loader, hparams)
+                vreport = ValidationReport(hparams, iteration, len(val_loader)) \
+                    if rank == 0 and getattr(hparams, 'validation_report', True) else None
+                val_loss, val_indiv = validate(gpu, model, criterion, val_loader, hparams, report=vreport)
                 if rank == 0:
                     _logger.info(f'Validation loss {iteration}: {val_loss:.6f} ')
                     remaining = int((hparams.nb_iterations - iteration) * (total_time / hparams.iters_check_for_model_improvement))
@@ -587,20 +643,29 @@ def train(gpu, hparams, log_file):
                     with open(metrics_path, 'a') as f:   # scalar names of DaftExprtLogger.log_validation (logger.py:41-45)
                         rec = {'iteration': iteration, 'DaftExprt.validation/loss': val_loss}
                         rec.update({f'DaftExprt.validation/{k}': v for k, v in val_indiv.items()})
+                        if vreport is not None:   # figures of DaftExprtLogger.log_validation (logger.py:55-157), as data
+                            report_dir = os.path.join(hparams.output_directory, 'validation')
+                            rec.update(vreport.write(report_dir))
+                            vreport.figures(report_dir)
+                            _logger.info(f'Validation report {iteration}: "{vreport.path(report_dir)}" in {vreport.seconds:.2f}s')
                         f.write(json.dumps(rec) + '\n')
                     if val_loss < best_val_loss:
                         _logger.info('Congrats!!! A new best model. You are the best!')
                         best_val_loss = val_loss
                         save_checkpoint(model, trainer.optimizer, hparams, lr, iteration, best_val_loss,
                                         os.path.join(ckpt_dir, 'DaftExprt_best'))
+                        generate_benchmark_sentences(model, hparams, os.path.join(ckpt_dir, 'best_checkpoint'), iteration)
                 if distributed:
                     dist.barrier()
             if iteration % hparams.iters_per_checkpoint == 0:
                 if rank == 0:
                     save_checkpoint(model, trainer.optimizer, hparams, lr, iteration, best_val_loss,
                                     os.path.join(ckpt_dir, f'DaftExprt_{iteration}'))
+                    generate_benchmark_sentences(model, hparams, os.path.join(ckpt_dir, f'chk_{iteration}'), iteration)
                 if distributed:
                     dist.barrier()
+            elif iteration >= hparams.nb_iterations and rank == 0:     # the end of training, when no checkpoint falls on it
+                generate_benchmark_sentences(model, hparams, os.path.join(ckpt_dir, f'chk_{iteration}'), iteration)
             iteration += 1
             if periodic:
                 start = time.time()          # validation / checkpoint time is not an iteration's duration (train.py:486)
