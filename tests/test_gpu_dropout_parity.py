@@ -77,7 +77,7 @@ def test_mask_behind_layernorm_is_the_restated_one(C, dtype):
 @pytest.mark.parametrize('H', [2, 8, 4])
 def test_attention_weight_mask_is_the_restated_one(H):
     ''' forward of every head size against softmax(QK^T) * mask @ V with the numpy mask; the backward kernels regenerate the same
-        mask (tests/test_gpu_kernels.py compares their gradients with the autograd of this forward form) '''
+        mask (tests/test_gpu_attention.py compares o, lse and every gradient element with the float64 form of this under the mask) '''
     from daft_exprt import ops
     torch.manual_seed(1)
     B, N, E, seed, p = 3, 203, 128, 0x1F2E3D4C5B6A7, 0.1
