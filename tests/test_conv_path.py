@@ -1,5 +1,5 @@
 """CPU-side check of dx_conv1d_ln_path, the one statement of which kernel a LayerNorm-fused GEMM runs on: literal cases and the paths
-the dispatch of csrc/conv_gemm.hip gives them (a host-only query: no GPU here)."""
+the dispatch of csrc/conv_gemm.hip (launch_ln, over the kernel units conv_sk.hip / conv_gemm_ln.hip / conv_gemm_lnbwd.hip) gives them (a host-only query: no GPU here)."""
 import os
 
 import pytest

@@ -28,7 +28,9 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=f
 
 
 def _sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.cpp')))
+    # largest first: a long unit must not queue behind short ones
+    srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.cpp')))
+    return sorted(srcs, key=lambda f: -os.path.getsize(os.path.join(CSRC, f)))
 
 
 def _headers_mtime():

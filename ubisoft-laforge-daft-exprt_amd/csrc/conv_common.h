@@ -1,5 +1,6 @@
-// helpers shared by the conv GEMM (conv_gemm.hip), weight-gradient (conv_wgrad.hip) and weight-packing (conv_pack.hip) units;
-// included INSIDE each unit's anonymous namespace
+// device helpers shared by the conv GEMM kernel units (conv_gemm_plain / _ln / _lnbwd, conv_wreg, conv_sk, conv_wide), the weight-gradient
+// unit (conv_wgrad.hip) and the weight-packing unit (conv_pack.hip); included INSIDE each unit's anonymous namespace.  conv_gemm.hip, the
+// host-side entry points, takes DX_ZERO_PAGE_EL from here.  (What the GEMM units share on the host side: conv_args.h.)
 #pragma once
 
 // zeros for the LDS-DMA lanes whose row lies outside the utterance / the weight matrix (read at offsets < 2 * Cin bytes)
@@ -46,4 +47,11 @@ __device__ __forceinline__ void store8<bf16_t>(bf16_t* p, const float* v) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) r[e] = (bf16_t)v[e];
   *reinterpret_cast<bf16x8*>(p) = r;
+}
+
+// one 1-KiB LDS-DMA piece (16 B per lane) to the LDS byte address `lds_dst` (conv_sk_kernel, conv_wide_kernel)
+__device__ __forceinline__ void sk_dma16(const void* gsrc, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }

@@ -95,7 +95,7 @@ def pack_conv_weight(w, dtype, transpose_flip=False, out=None):
     return out
 
 
-# Which kernel a GEMM runs on is decided in csrc/conv_gemm.hip.  For the LayerNorm-fused GEMMs `ln_path` asks that decision
+# Which kernel a GEMM runs on is decided on the C side (csrc/conv_gemm.hip and the launchers of the kernel units behind it).  For the LayerNorm-fused GEMMs `ln_path` asks that decision
 # (dx_conv1d_ln_path) and nothing here restates it.  The wide and the register-weights kernel have no host query: their shape rules are
 # stated once each below (tests/test_gpu_conv.py asserts the predicates and then runs the entry points, which check the same on their side).
 LN_SPLITK, LN_PLAN_K3, LN_PLAN_K1, LN_ROWS128, LN_ROWS64 = range(5)    # DX_LN_PATH_* of include/daft_exprt_hip.h
