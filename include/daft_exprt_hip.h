@@ -672,6 +672,36 @@ int dx_film_hist_count(const float* film, const double* edges, const int* finite
 int dx_alignment_score(const float* weights, const int64_t* durations_int, const int64_t* in_lengths, const int64_t* out_lengths,
                        int64_t* frames, int64_t* hits, float* mass, int B, int L, int T, void* stream);
 
+/* ---- K24: the HiFi-GAN generator (Kong et al. 2020, `models.py` of jik876/hifi-gan) as batched inference -- the vocoder the
+ * fine-tuning data set of K19 exists to train.  Additive entry points.  Activations are TIME-MAJOR fp32: (B, N, C) with rows
+ * (samples) ld* floats apart and utterance b at row b * N; n_rows (B) int64 = the live rows of each utterance.  Rows < 0 or
+ * >= n_rows[b] of an input are zeros and are NEVER READ; an output's rows >= n_rows[b] are written as zeros up to N, so an utterance
+ * gets the same bits alone, in any batch, in any sub-batch.  No atomics, no split-K.  x, w_packed 16-byte aligned.
+ *
+ * dx_voc_conv: v = Conv1d(Cin, Cout, taps, dilation, padding dilation (taps - 1) / 2)(leaky_relu(x, in_slope)) + bias [+ residual]
+ * (in_slope = 1: no activation).  w_packed [tap][Cout][Cin] in w_dtype = the operand type: DX_BF16 (v_mfma_f32_32x32x16_bf16, the
+ * post-activation input rounded to bf16 at operand load) or DX_F32 (v_mfma_f32_32x32x2_f32, exact); accumulation fp32.
+ *   y   NULL or (B, N, Cout): y = v;       residual NULL or laid out like y (may be y itself, never x);
+ *   acc NULL or (B, N, Cout): acc = acc_scale * v when acc_init, acc += acc_scale * v otherwise -- the mean over the ResBlocks of
+ *       a stage costs no launch of its own.
+ * An input tile with its halo is staged in LDS once per 32-channel slice and read by every tap.  Cin and Cout multiples of 32 and
+ * (taps - 1) * dilation <= 64 run on MFMA; anything else runs a plain VALU kernel of the same contract (correctness only).
+ *
+ * dx_voc_upsample: y (B, N * u, Cout) = ConvTranspose1d(Cin, Cout, k, stride u, padding (k - u) / 2)(leaky_relu(x, in_slope)) + bias,
+ * x (B, N, Cin), as u polyphase convs through the same kernels: output row t u + p sums the taps j = j0 + s u, j0 = (p + pad) mod u,
+ * of input rows t + (p + pad) div u - s.  w_packed [u][ceil(k / u)][Cout][Cin], entry (p, s) = weight[:, :, j]^T, zeros where j >= k.
+ * k >= u, k - u even.  n_rows counts INPUT rows; output rows >= n_rows[b] * u are zeros.
+ *
+ * dx_voc_post: y (B, ldy) fp32, y[b, t] = tanh(Conv1d(C, 1, taps)(leaky_relu(x, in_slope))[t] + bias) for t < n_rows[b], 0 up to N.
+ * w [tap][C] fp32, bias one float or NULL.  A VALU reduction, fp32 throughout. */
+int dx_voc_conv(const float* x, long ldx, const void* w_packed, int w_dtype, const float* bias, const float* residual, long ldr,
+                float* y, long ldy, float* acc, long lda, float acc_scale, int acc_init, const int64_t* n_rows, int B, int N,
+                int Cin, int Cout, int taps, int dilation, float in_slope, void* stream);
+int dx_voc_upsample(const float* x, long ldx, const void* w_packed, int w_dtype, const float* bias, float* y, long ldy,
+                    const int64_t* n_rows, int B, int N, int Cin, int Cout, int k, int u, float in_slope, void* stream);
+int dx_voc_post(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, const int64_t* n_rows, int B, int N,
+                int C, int taps, float in_slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

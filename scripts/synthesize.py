@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Batched prosody-transfer synthesis with objective scores, behind the flags of the reference's `scripts/synthesize.py`:
-    python scripts/synthesize.py -out OUT_DIR -chk CHECKPOINT -tf SENTENCES -sb STYLE_BANK [-bs N] [-rtf] [-ctrl]
+    python scripts/synthesize.py -out OUT_DIR -chk CHECKPOINT -tf SENTENCES -sb STYLE_BANK [-bs N] [-rtf] [-ctrl] [-voc G_CKPT [-vcfg JSON]]
 
   -tf   phonemised sentences, one `file_name|{P1 P2} {P3} , {P4} ? ~` per line: the `sentences_to_generate.txt` the reference
         writes after text cleaning and MFA g2p, which stay outside this project (`generate.read_phonemised_sentences`)
@@ -8,11 +8,16 @@
         the GPU as one batch
   -rtf  an extra pass without audio that logs the real-time factor at this batch size
   -ctrl the reference's control example instead of plain transfer: every symbol 1.25 times longer, pitch shifted by +50 Hz
+  -voc  a HiFi-GAN generator checkpoint (`torch.save({'generator': state_dict})`, e.g. one fine-tuned on this project's
+        `fine_tuning_dataset`); -vcfg its `config.json` (default: the one beside the checkpoint).  The `.wav` files are then the
+        vocoder's audio (16-bit PCM) instead of the Griffin-Lim preview, the scores refer to that audio, and -rtf logs a second
+        real-time factor that includes the vocoder
 
 Every sentence gets a random reference of the style bank and a random speaker (`random.seed(1234)`), is synthesised with
 Griffin-Lim preview audio and scored on the device against its reference: `<out>/prosody_transfer.json` holds, per output file,
 the pitch and energy correlation (`daft_exprt/evaluate.py`; null where undefined) and the frame counts, and a summary with the
-mean and median of the defined values and the number of undefined ones.  Without -ctrl each preview is renamed to
+mean and median of the defined values and the number of undefined ones, and `"audio"`: which audio was scored ("hifi-gan" with
+-voc, else "griffin-lim").  Without -ctrl each preview is renamed to
 `<idx>_<name>.wav` and a copy of its reference recording is put beside it as `<idx>_ref.wav`, so that the two sort together."""
 import argparse
 import json
@@ -64,8 +69,17 @@ def n_symbols(sentence):
     return sum(len(item) if isinstance(item, (list, tuple)) else 1 for item in sentence)
 
 
-def run(args, model, hparams, control=None, audio=True, scores=None):
-    ''' one pass over the sentence file; returns [(sentence index, output name, reference .npz)] in sentence order '''
+def load_vocoder(checkpoint, config, hparams):
+    ''' the HiFi-GAN generator on cuda:0, checked against the acoustic model's mel front-end '''
+    from daft_exprt.vocoder import Vocoder
+    vocoder = Vocoder.from_checkpoint(checkpoint, config, compute_dtype=hparams.compute_dtype, device='cuda:0')
+    vocoder.check_hparams(hparams)
+    return vocoder
+
+
+def run(args, model, hparams, control=None, audio=True, scores=None, vocoder=None):
+    ''' one pass over the sentence file; returns [(sentence index, output name, reference .npz)] in sentence order.  With a
+        vocoder the audio is its own; `audio` then only decides whether the pass is timed '''
     sentences, names = generate.read_phonemised_sentences(args.text_file, hparams.symbols)
     bank = style_bank(args.style_bank, hparams)
     refs = [random.choice(bank) for _ in sentences]
@@ -76,8 +90,9 @@ def run(args, model, hparams, control=None, audio=True, scores=None):
         pitch = [control['pitch_transform'], [[control['pitch']] * n_symbols(s) for s in sentences]]
     os.makedirs(args.output_dir, exist_ok=True)
     predictions = generate.generate_mel_specs(model, sentences, list(names), speakers, refs, args.output_dir, hparams, dur_factors=dur,
-                                              pitch_factors=pitch, batch_size=args.batch_size, use_griffin_lim=audio,
-                                              get_time_perf=not audio, scores=scores)
+                                              pitch_factors=pitch, batch_size=args.batch_size,
+                                              use_griffin_lim=audio and vocoder is None, get_time_perf=not audio, scores=scores,
+                                              vocoder=vocoder)
     outputs = []
     for idx, name in enumerate(names):      # the driver returns its own names, a batch at a time in order of length
         mine = [key for key in predictions if key.startswith(f'{name}_spk_{speakers[idx]}_ref_')]
@@ -112,14 +127,15 @@ def summarise(entries):
     return summary
 
 
-def write_scores(args, scores, wav_names):
-    ''' `<out>/prosody_transfer.json`: {'files': {name: scores + 'wav'}, 'summary': ...}; NaN is written as null '''
+def write_scores(args, scores, wav_names, audio='griffin-lim'):
+    ''' `<out>/prosody_transfer.json`: {'audio': which audio was scored, 'files': {name: scores + 'wav'}, 'summary': ...}; NaN is
+        written as null '''
     entries = {}
     for name, values in scores.items():
         entry = {k: (None if isinstance(v, float) and math.isnan(v) else v) for k, v in values.items()}
         entry['wav'] = f'{wav_names.get(name, name)}.wav'
         entries[name] = entry
-    report = {'files': entries, 'summary': summarise(entries)}
+    report = {'audio': audio, 'files': entries, 'summary': summarise(entries)}
     path = os.path.join(args.output_dir, 'prosody_transfer.json')
     with open(path, 'w', encoding='utf-8') as f:
         json.dump(report, f, indent=1)
@@ -143,16 +159,23 @@ def main():
     parser.add_argument('-bs', '--batch_size', type=int, default=50, help='sentences per inference call')
     parser.add_argument('-rtf', '--real_time_factor', action='store_true', help='first time a pass without audio and log its real-time factor')
     parser.add_argument('-ctrl', '--control', action='store_true', help='apply the duration x 1.25, pitch + 50 Hz example to every symbol')
+    parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN generator checkpoint: write and score its audio instead of the Griffin-Lim preview')
+    parser.add_argument('-vcfg', '--vocoder_config', default=None, help='HiFi-GAN config.json (default: beside the vocoder checkpoint)')
     args = parser.parse_args()
     logging.basicConfig(format='%(asctime)s [%(levelname)s] %(message)s', datefmt='%Y-%m-%d %H:%M:%S', level=logging.INFO)
     random.seed(1234)
 
     model, hparams = load_model(args.checkpoint)
+    vocoder = load_vocoder(args.vocoder, args.vocoder_config, hparams) if args.vocoder else None
     if args.real_time_factor:
         run(args, model, hparams, audio=False)
+        if vocoder is not None:
+            run(args, model, hparams, audio=False, vocoder=vocoder)
+            _logger.info(f'DaftExprt + HiFi-GAN RTF: {generate.LAST_TIME_PERF["rtf"]:.2f}')
     scores = {}
-    outputs = run(args, model, hparams, control=CONTROL if args.control else None, scores=scores)
-    write_scores(args, scores, {} if args.control else pair_with_references(args, outputs))
+    outputs = run(args, model, hparams, control=CONTROL if args.control else None, scores=scores, vocoder=vocoder)
+    write_scores(args, scores, {} if args.control else pair_with_references(args, outputs),
+                 audio='hifi-gan' if vocoder is not None else 'griffin-lim')
 
 
 if __name__ == '__main__':

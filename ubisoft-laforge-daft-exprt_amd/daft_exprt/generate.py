@@ -3,7 +3,7 @@
 Keeps the hot-path part of the reference driver (`src/daft_exprt/generate.py`): `collate_tensors` (140-239: symbol ids,
 per-symbol duration / energy / pitch control factors, reference `.npz` prosody, sort by symbol count, padding rules),
 `generate_batch_mel_specs` (242-317: one `model.inference` call per batch, crop per item, `.npz` with the same keys,
-Griffin-Lim preview `.wav` per item on the GPU, `daft_exprt/griffin_lim.py`) and `generate_mel_specs` (320-437: chunking +
+Griffin-Lim preview `.wav` per item on the GPU, `daft_exprt/griffin_lim.py`, or HiFi-GAN audio, `daft_exprt/vocoder.py`) and `generate_mel_specs` (320-437: chunking +
 real-time-factor accounting) and `extract_reference_parameters` (440-462: a reference recording -> the `.npz` of energy, pitch
 and mel-spectrogram the collate reads; wav reading, resampling, pitch and mel all on the GPU).  Text phonemisation (MFA g2p) and plots are outside the accelerated path (SURVEY 2, rows
 6/13/15): sentences arrive phonemised --
@@ -94,7 +94,7 @@ def _ref_name(ref, idx):
 
 def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_factors, batch_energy_factors, batch_pitch_factors,
                              pitch_transform, batch_speaker_ids, batch_file_names, output_dir, hparams, n_jobs=1,
-                             use_griffin_lim=True, scores=None):
+                             use_griffin_lim=True, scores=None, vocoder=None):
     ''' `generate.py:242-317`, same contract: every file name gets the `_spk_<id>_ref_<reference>` suffix IN PLACE
         (the caller's list is updated like the reference does, 248-253), one `model.inference` call on the collated
         batch, `<output_dir>/<file_name>.npz` holding `mel_spec` (298), and the return value
@@ -103,12 +103,16 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         copy to the host (`griffin_lim.griffin_lim_batch`, 30 iterations, device noise seeded with 0) and written as
         `<output_dir>/<file_name>.wav`: mono, `hparams.sampling_rate`, 64-bit float, peak 1.  Plots stay outside the
         accelerated path.
-        `scores` (an extension; needs `use_griffin_lim`): a dict that receives, per file name, the prosody-transfer scores of
-        the preview audio against its reference (`evaluate.prosody_transfer_scores`, computed on the device beside the audio):
+        `scores` (an extension; needs `use_griffin_lim` or `vocoder`): a dict that receives, per file name, the prosody-transfer scores of
+        the generated audio against its reference (`evaluate.prosody_transfer_scores`, computed on the device beside the audio):
         `pitch_pcc`, `energy_pcc` (floats, NaN where undefined), `voiced_ref`, `voiced_gen`, `frames_ref`, `frames_gen` (ints).
-        With None nothing is computed and nothing else changes. '''
-    if scores is not None and not use_griffin_lim:
-        raise ValueError('scores are computed from the Griffin-Lim preview audio: pass use_griffin_lim=True')
+        With None nothing is computed and nothing else changes.
+        `vocoder` (an extension): a `vocoder.Vocoder` (HiFi-GAN generator).  `<file_name>.wav` is then the vocoder's audio of the
+        decoder's mel, made on the device before the copy to the host and written as 16-bit PCM (`audio.write_wav_int16`,
+        `n_frames * hop` samples); `use_griffin_lim` is not needed and no preview is made; `scores` are computed on the vocoder's
+        audio.  With None nothing changes. '''
+    if scores is not None and not use_griffin_lim and vocoder is None:
+        raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
     for idx, file_name in enumerate(batch_file_names):
         file_name += f'_spk_{batch_speaker_ids[idx]}'
         file_name += f'_ref_{_ref_name(batch_refs[idx], idx)}'
@@ -127,9 +131,15 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
     inputs = tuple(t.to(gpu, non_blocking=True) for t in col[:-1])
     inference = model.inference if hasattr(model, 'inference') else model.module.inference   # DDP-wrapped callers (270-278)
     encoder_preds, decoder_preds, alignments = inference(inputs, pitch_transform, hparams)
-    if use_griffin_lim:
+    if vocoder is not None:
+        from daft_exprt.vocoder import pcm16
+        vocoder.check_hparams(hparams)
+        wavs, n_samples = vocoder(decoder_preds[0].float().contiguous(), decoder_preds[1])
+        pcm = pcm16(wavs)
+    elif use_griffin_lim:
         from daft_exprt import griffin_lim
         wavs, n_samples = griffin_lim.griffin_lim_batch(decoder_preds[0].float().contiguous(), decoder_preds[1], hparams)
+    if vocoder is not None or use_griffin_lim:
         if scores is not None:
             from daft_exprt import evaluate
             batch_scores = evaluate.prosody_transfer_scores(wavs, n_samples, inputs[6], inputs[5], inputs[8], hparams)
@@ -143,10 +153,16 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         np.savez(os.path.join(output_dir, f'{name}.npz'), mel_spec=mel_spec[i, :, :t])
         predictions[f'{name}'] = [duration[i, :l], duration_int[i, :l], energy[i, :l], pitch[i, :l], mel_spec[i, :, :t],
                                   weights[i, :l, :t]]
-    if use_griffin_lim:
+    if vocoder is not None:
+        from daft_exprt import audio
+        pcm, n_samples = pcm.cpu().numpy(), n_samples.cpu().numpy()
+        for i, name in enumerate(file_names):
+            audio.write_wav_int16(os.path.join(output_dir, f'{name}.wav'), hparams.sampling_rate, pcm[i, :int(n_samples[i])])
+    elif use_griffin_lim:
         wavs, n_samples = wavs.cpu().numpy(), n_samples.cpu().numpy()
         for i, name in enumerate(file_names):
             griffin_lim.write_wav(os.path.join(output_dir, f'{name}.wav'), hparams.sampling_rate, wavs[i, :int(n_samples[i])])
+    if vocoder is not None or use_griffin_lim:
         if scores is not None:
             host = {key: t.cpu().tolist() for key, t in batch_scores.items()}
             for i, name in enumerate(file_names):
@@ -284,15 +300,15 @@ LAST_TIME_PERF = {}   # filled by generate_mel_specs(get_time_perf=True): what t
 
 def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_dir, hparams, dur_factors=None,
                        energy_factors=None, pitch_factors=None, batch_size=1, n_jobs=1, use_griffin_lim=False,
-                       get_time_perf=False, scores=None):
+                       get_time_perf=False, scores=None, vocoder=None):
     ''' `generate.py:320-437`, same contract: `pitch_factors = [transform, [per-sentence factor lists]]`, the list-length
         asserts, eval mode + no grad, chunks of `batch_size`, returns the predictions dict only.  With `get_time_perf`
         the real-time factor is logged exactly like the reference: wall time of the whole per-batch function (collate,
         H2D, inference, D2H, file writes) against `((n_frames - 1) * hop + n_fft - 2 * (n_fft // 2)) / sr` seconds of
-        audio per sentence (413-435); the numbers are also left in `LAST_TIME_PERF`.  `scores`: see
-        `generate_batch_mel_specs`. '''
-    if scores is not None and not use_griffin_lim:
-        raise ValueError('scores are computed from the Griffin-Lim preview audio: pass use_griffin_lim=True')
+        audio per sentence (413-435); the numbers are also left in `LAST_TIME_PERF`.  `scores`, `vocoder`:
+        see `generate_batch_mel_specs`. '''
+    if scores is not None and not use_griffin_lim and vocoder is None:
+        raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
     n = len(sentences)
     dur_factors = [None for _ in range(n)] if dur_factors is None else dur_factors
     energy_factors = [None for _ in range(n)] if energy_factors is None else energy_factors
@@ -313,7 +329,7 @@ def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_d
             b_sent, b_refs, b_dur, b_en, b_pi, b_spk, b_names = chunk
             begin = time.time() if get_time_perf else None
             predictions.update(generate_batch_mel_specs(model, b_sent, b_refs, b_dur, b_en, b_pi, pitch_transform, b_spk,
-                                                        b_names, output_dir, hparams, n_jobs, use_griffin_lim, scores))
+                                                        b_names, output_dir, hparams, n_jobs, use_griffin_lim, scores, vocoder))
             time_per_batch += [time.time() - begin] if get_time_perf else []
     if get_time_perf:
         durations = []

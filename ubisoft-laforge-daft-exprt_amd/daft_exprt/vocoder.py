@@ -1,0 +1,306 @@
+"""HiFi-GAN generator (Kong et al. 2020, `jik876/hifi-gan` `models.py`) as batched inference on the GPU: the vocoder the
+`fine_tune` data set exists to train, from a standard HiFi-GAN checkpoint + `config.json` to waveforms.
+
+    x = conv_pre(mel)                                                   Conv1d(num_mels, C0, 7)
+    per stage i:  x = ups.i(leaky_relu(x, 0.1))                         ConvTranspose1d(C0 >> i, C0 >> (i + 1), k, stride u)
+                  x = mean_j ResBlock[i * nk + j](x)                    kernels / dilations of the config, type "1" or "2"
+    wav = tanh(conv_post(leaky_relu(x, 0.01)))                          Conv1d(C_last, 1, 7)
+
+Weight norm is folded once at load time (float64, plain torch: plumbing); every convolution runs in csrc/vocoder.hip
+(`dx_voc_conv`, `dx_voc_upsample`, `dx_voc_post`) on time-major fp32 activations with bf16 or fp32 MFMA operands.  Sequence ends
+follow the dead-row contract: every layer treats the rows past an utterance's end as zeros without reading them, so an utterance
+gets the same bits alone, in a ragged batch and in any sub-batch.  No CPU fallback: without the HIP library / a GPU this raises.
+"""
+import json
+import math
+import os
+
+import torch
+
+from daft_exprt import _hip as H
+from daft_exprt import config as _config
+
+LRELU_SLOPE = 0.1
+POST_SLOPE = 0.01           # F.leaky_relu's default in front of conv_post (models.py), not the 0.1 used everywhere else
+DEFAULT_WORKSPACE_BYTES = 8 << 30
+_CONFIG_LISTS = ('upsample_rates', 'upsample_kernel_sizes', 'resblock_kernel_sizes', 'resblock_dilation_sizes')
+_CONFIG_KEYS = ('resblock',) + _CONFIG_LISTS + ('upsample_initial_channel', 'num_mels', 'hop_size', 'sampling_rate')
+
+
+def load_config(config):
+    ''' a dict, or the path of a HiFi-GAN `config.json` '''
+    if isinstance(config, (str, os.PathLike)):
+        with open(config, 'r', encoding='utf-8') as f:
+            config = json.load(f)
+    return dict(config)
+
+
+def validate_config(cfg):
+    ''' raises ValueError naming the offending key '''
+    for key in _CONFIG_KEYS:
+        if key not in cfg:
+            raise ValueError(f'vocoder config: "{key}" is missing')
+    if str(cfg['resblock']) not in ('1', '2'):
+        raise ValueError(f'vocoder config: "resblock" is {cfg["resblock"]!r}, expected "1" or "2"')
+    for key in _CONFIG_LISTS:
+        if not isinstance(cfg[key], (list, tuple)) or len(cfg[key]) == 0:
+            raise ValueError(f'vocoder config: "{key}" must be a non-empty list')
+    rates, kernels = list(cfg['upsample_rates']), list(cfg['upsample_kernel_sizes'])
+    if len(kernels) != len(rates):
+        raise ValueError(f'vocoder config: "upsample_kernel_sizes" has {len(kernels)} entries for {len(rates)} "upsample_rates"')
+    if len(cfg['resblock_dilation_sizes']) != len(cfg['resblock_kernel_sizes']):
+        raise ValueError(f'vocoder config: "resblock_dilation_sizes" has {len(cfg["resblock_dilation_sizes"])} lists for '
+                         f'{len(cfg["resblock_kernel_sizes"])} "resblock_kernel_sizes"')
+    for k in cfg['resblock_kernel_sizes']:
+        if int(k) < 1 or int(k) % 2 == 0:
+            raise ValueError(f'vocoder config: "resblock_kernel_sizes" holds {k}: kernels must be odd')
+    for dils in cfg['resblock_dilation_sizes']:
+        if not isinstance(dils, (list, tuple)) or len(dils) == 0 or any(int(d) < 1 for d in dils):
+            raise ValueError(f'vocoder config: "resblock_dilation_sizes" holds {dils!r}: expected lists of dilations >= 1')
+    for u, k in zip(rates, kernels):
+        if int(u) < 1 or int(k) < int(u) or (int(k) - int(u)) % 2:
+            raise ValueError(f'vocoder config: "upsample_kernel_sizes" {k} with rate {u}: need k >= u and k - u even')
+    c0 = int(cfg['upsample_initial_channel'])
+    if c0 < 1 or c0 % (1 << len(rates)):
+        raise ValueError(f'vocoder config: "upsample_initial_channel" {c0} is not divisible by 2^{len(rates)}')
+    if int(cfg['num_mels']) < 1:
+        raise ValueError(f'vocoder config: "num_mels" is {cfg["num_mels"]}')
+    if math.prod(int(u) for u in rates) != int(cfg['hop_size']):
+        raise ValueError(f'vocoder config: "hop_size" {cfg["hop_size"]} is not the product of "upsample_rates" {rates}')
+
+
+def layer_table(cfg):
+    ''' [(state-dict name, kind, weight shape, dilation)] in forward order; kind: 'conv' (Cout, Cin, k) or 'up' (Cin, Cout, k) '''
+    c0, nk = int(cfg['upsample_initial_channel']), len(cfg['resblock_kernel_sizes'])
+    layers = [('conv_pre', 'conv', (c0, int(cfg['num_mels']), 7), 1)]
+    for i, (u, k) in enumerate(zip(cfg['upsample_rates'], cfg['upsample_kernel_sizes'])):
+        c = c0 >> (i + 1)
+        layers.append((f'ups.{i}', 'up', (c0 >> i, c, int(k)), 1))
+        for j, (rk, dils) in enumerate(zip(cfg['resblock_kernel_sizes'], cfg['resblock_dilation_sizes'])):
+            for m, d in enumerate(dils):
+                if str(cfg['resblock']) == '1':
+                    layers.append((f'resblocks.{i * nk + j}.convs1.{m}', 'conv', (c, c, int(rk)), int(d)))
+                    layers.append((f'resblocks.{i * nk + j}.convs2.{m}', 'conv', (c, c, int(rk)), 1))
+                else:
+                    layers.append((f'resblocks.{i * nk + j}.convs.{m}', 'conv', (c, c, int(rk)), int(d)))
+    layers.append(('conv_post', 'conv', (1, c0 >> len(cfg['upsample_rates']), 7), 1))
+    return layers
+
+
+_NORM_FORMS = (('.weight_g', '.weight_v'), ('.parametrizations.weight.original0', '.parametrizations.weight.original1'))
+
+
+def folded_weight(state_dict, name):
+    ''' the layer's weight as float64: plain `.weight`, or g * v / ||v|| with the norm over every axis but 0 (Cout of a Conv1d,
+        Cin of a ConvTranspose1d -- torch's weight_norm default dim=0 on either) '''
+    if f'{name}.weight' in state_dict:
+        return state_dict[f'{name}.weight'].detach().double().cpu()
+    for g_key, v_key in _NORM_FORMS:
+        if f'{name}{g_key}' in state_dict and f'{name}{v_key}' in state_dict:
+            g, v = state_dict[f'{name}{g_key}'].detach().double().cpu(), state_dict[f'{name}{v_key}'].detach().double().cpu()
+            if v.dim() != 3 or g.numel() != v.shape[0]:
+                raise ValueError(f'vocoder checkpoint: "{name}{g_key}" has shape {tuple(g.shape)} for a weight of {tuple(v.shape)}')
+            return g.reshape(-1, 1, 1) * v / v.flatten(1).norm(dim=1).reshape(-1, 1, 1)
+    raise ValueError(f'vocoder checkpoint: "{name}" has neither .weight, .weight_g/.weight_v nor .parametrizations.weight.original0/1')
+
+
+def folded_state(cfg, state_dict):
+    ''' {name: (weight float64, bias float64)} of every layer, shapes checked against the config '''
+    out = {}
+    for name, _, shape, _ in layer_table(cfg):
+        w = folded_weight(state_dict, name)
+        if tuple(w.shape) != shape:
+            raise ValueError(f'vocoder checkpoint: "{name}" weight has shape {tuple(w.shape)}, the config gives {shape}')
+        if f'{name}.bias' not in state_dict:
+            raise ValueError(f'vocoder checkpoint: "{name}.bias" is missing')
+        b = state_dict[f'{name}.bias'].detach().double().cpu()
+        n_out = shape[1] if name.startswith('ups.') else shape[0]
+        if tuple(b.shape) != (n_out,):
+            raise ValueError(f'vocoder checkpoint: "{name}.bias" has shape {tuple(b.shape)}, expected ({n_out},)')
+        out[name] = (w, b)
+    return out
+
+
+def pack_conv_weight(w, dtype, cin_pad=None):
+    ''' Conv1d weight (Cout, Cin, k) -> [k][Cout][Cin (zero-padded to cin_pad)] '''
+    cout, cin, k = w.shape
+    p = torch.zeros((k, cout, cin_pad or cin), dtype=torch.float64)
+    p[:, :, :cin] = w.permute(2, 0, 1)
+    return p.to(dtype).contiguous()
+
+
+def pack_upsample_weight(w, u, dtype):
+    ''' ConvTranspose1d weight (Cin, Cout, k) -> [u][ceil(k / u)][Cout][Cin]: entry (p, s) is tap j = (p + pad) mod u + s u,
+        zeros where j >= k '''
+    cin, cout, k = w.shape
+    pad, taps = (k - u) // 2, -(-k // u)
+    p = torch.zeros((u, taps, cout, cin), dtype=torch.float64)
+    for phase in range(u):
+        for s in range(taps):
+            j = (phase + pad) % u + s * u
+            if j < k:
+                p[phase, s] = w[:, :, j].t()
+    return p.to(dtype).contiguous()
+
+
+def pcm16(wavs):
+    ''' [-1, 1] fp32 -> int16 as HiFi-GAN's inference writes it (x 32768, truncated toward zero), saturating instead of wrapping '''
+    return (wavs * 32768.).clamp(-32768., 32767.).to(torch.int16)
+
+
+class Vocoder:
+    def __init__(self, config, state_dict, compute_dtype='bf16', device=None):
+        ''' config: dict or path of `config.json`; state_dict: the checkpoint's 'generator' entry, in any of the three key forms;
+            compute_dtype: 'bf16' (bf16 MFMA operands, fp32 accumulation and residual stream) or 'fp32' (exact fp32 MFMA) '''
+        self.config = load_config(config)
+        validate_config(self.config)
+        if compute_dtype not in ('bf16', 'fp32'):
+            raise ValueError(f'compute_dtype is {compute_dtype!r}, expected "bf16" or "fp32"')
+        cfg = self.config
+        self.compute_dtype = compute_dtype
+        self.device = H.device(device)
+        self.rates = [int(u) for u in cfg['upsample_rates']]
+        self.up_kernels = [int(k) for k in cfg['upsample_kernel_sizes']]
+        self.res_kernels = [int(k) for k in cfg['resblock_kernel_sizes']]
+        self.res_dilations = [[int(d) for d in dils] for dils in cfg['resblock_dilation_sizes']]
+        self.resblock = str(cfg['resblock'])
+        self.c0, self.num_mels = int(cfg['upsample_initial_channel']), int(cfg['num_mels'])
+        self.hop, self.sampling_rate = int(cfg['hop_size']), int(cfg['sampling_rate'])
+        folded = folded_state(cfg, state_dict)
+        dt = torch.bfloat16 if compute_dtype == 'bf16' else torch.float32
+        self._wdt = H.BF16 if compute_dtype == 'bf16' else H.F32
+        # conv_pre on the MFMA kernel: its input channels (80 mel bins) are zero-padded to a multiple of 32
+        self.mel_channels = -(-self.num_mels // 32) * 32 if self.c0 % 32 == 0 else self.num_mels
+        self._layers = {}
+        for name, kind, shape, dil in layer_table(cfg):
+            w, b = folded[name]
+            if name == 'conv_post':
+                packed = w[0].t().contiguous().float()                                    # [tap][C] fp32
+            elif kind == 'up':
+                packed = pack_upsample_weight(w, self.rates[int(name.split('.')[1])], dt)
+            else:
+                packed = pack_conv_weight(w, dt, self.mel_channels if name == 'conv_pre' else None)
+            self._layers[name] = (packed.to(self.device), b.float().to(self.device), shape, dil)
+        self._ws = None
+
+    @classmethod
+    def from_checkpoint(cls, path, config=None, compute_dtype='bf16', device=None):
+        ''' a `torch.save`d dict whose 'generator' entry is the state dict (HiFi-GAN's `g_XXXXXXXX`); `config` defaults to
+            `config.json` beside the checkpoint, as HiFi-GAN lays it out '''
+        if config is None:
+            config = os.path.join(os.path.dirname(os.path.abspath(path)), 'config.json')
+        ckpt = torch.load(path, map_location='cpu', weights_only=False)
+        if not isinstance(ckpt, dict) or 'generator' not in ckpt:
+            raise ValueError(f'{path}: no "generator" entry (expected a HiFi-GAN generator checkpoint)')
+        return cls(config, ckpt['generator'], compute_dtype=compute_dtype, device=device)
+
+    def check_hparams(self, hparams):
+        ''' raises ValueError unless the vocoder was trained on this front-end's mels '''
+        if math.prod(self.rates) != int(hparams.hop_length):
+            raise ValueError(f'vocoder "upsample_rates" {self.rates} multiply to {math.prod(self.rates)}, hparams.hop_length is {hparams.hop_length}')
+        if self.num_mels != int(hparams.n_mel_channels):
+            raise ValueError(f'vocoder "num_mels" is {self.num_mels}, hparams.n_mel_channels is {hparams.n_mel_channels}')
+        if self.sampling_rate != int(hparams.sampling_rate):
+            raise ValueError(f'vocoder "sampling_rate" is {self.sampling_rate}, hparams.sampling_rate is {hparams.sampling_rate}')
+
+    # ---- launches ---------------------------------------------------------------------------------------------------------
+    def _conv(self, name, x, y, n, res=None, acc=None, acc_scale=0., acc_init=False, slope=LRELU_SLOPE):
+        w, b, (cout, cin, k), dil = self._layers[name]
+        B, N, ldx = x.shape
+        H.check(H.lib().dx_voc_conv(H.ptr(x), ldx, H.ptr(w), self._wdt, H.ptr(b), H.ptr(res), cout, H.ptr(y), cout, H.ptr(acc), cout,
+                                    float(acc_scale), int(acc_init), H.ptr(n), B, N, w.shape[2], cout, k, dil, float(slope), H.stream()))
+
+    def _upsample(self, name, x, y, n, u):
+        w, b, (cin, cout, k), _ = self._layers[name]
+        B, N, _ = x.shape
+        H.check(H.lib().dx_voc_upsample(H.ptr(x), cin, H.ptr(w), self._wdt, H.ptr(b), H.ptr(y), cout, H.ptr(n), B, N, cin, cout, k, u,
+                                        LRELU_SLOPE, H.stream()))
+
+    def _post(self, x, out, n):
+        w, bias, _, _ = self._layers['conv_post']
+        B, N, c = x.shape
+        H.check(H.lib().dx_voc_post(H.ptr(x), c, H.ptr(w), H.ptr(bias), H.ptr(out), out.stride(0), H.ptr(n), B, N, c, 7, POST_SLOPE,
+                                    H.stream()))
+
+    def _elements_per_utterance(self, T):
+        ''' (floats of the largest activation of one utterance of T frames, floats of its padded mel) '''
+        rows, most = T, T * self.c0
+        for i, u in enumerate(self.rates):
+            rows *= u
+            most = max(most, rows * (self.c0 >> (i + 1)))
+        return most, T * self.mel_channels
+
+    def _run(self, mel, lengths, out, T):
+        ''' one sub-batch: mel (b, num_mels, >= T), lengths (b,) clamped to [0, T], out (b, >= T * hop) '''
+        b = mel.shape[0]
+        most, mel_el = self._elements_per_utterance(T)
+        need = b * (6 * most + mel_el)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        if _config.POISON:
+            self._ws.fill_(float('nan'))
+        bufs = [self._ws[i * b * most:(i + 1) * b * most] for i in range(6)]
+        melt = self._ws[6 * b * most:need].view(b, T, self.mel_channels)
+        melt[:, :, :self.num_mels] = mel[:, :, :T].transpose(1, 2)
+        if self.mel_channels > self.num_mels:
+            melt[:, :, self.num_mels:] = 0.
+        view = lambda buf, rows, c: buf[:b * rows * c].view(b, rows, c)      # noqa: E731
+        x, up, ping, pong, tmp, total = bufs
+        rows, c, n = T, self.c0, lengths
+        xv = view(x, rows, c)
+        self._conv('conv_pre', melt, xv, n, slope=1.)
+        nk = len(self.res_kernels)
+        for i, u in enumerate(self.rates):
+            c_out = c >> 1
+            upv = view(up, rows * u, c_out)
+            self._upsample(f'ups.{i}', xv, upv, n, u)
+            rows, c, n = rows * u, c_out, n * u
+            tv, sv = view(tmp, rows, c), view(total, rows, c)
+            for j, dils in enumerate(self.res_dilations):
+                cur, block = upv, f'resblocks.{i * nk + j}'
+                for m in range(len(dils)):
+                    nxt = view(ping if cur.data_ptr() != ping.data_ptr() else pong, rows, c)
+                    last = m == len(dils) - 1
+                    tail = dict(res=cur, acc=sv if last else None, acc_scale=1. / nk, acc_init=j == 0)
+                    if self.resblock == '1':
+                        self._conv(f'{block}.convs1.{m}', cur, tv, n)
+                        self._conv(f'{block}.convs2.{m}', tv, None if last else nxt, n, **tail)
+                    else:
+                        self._conv(f'{block}.convs.{m}', cur, None if last else nxt, n, **tail)
+                    cur = nxt
+            x, total = total, x
+            xv = view(x, rows, c)
+        self._post(xv, out, n)
+
+    def __call__(self, mel, lengths, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
+        ''' mel (B, num_mels, T) natural-log mel on the device (what `inference` returns as `decoder_preds[0]`; columns at or
+            past `lengths` may hold anything, they are not read), lengths (B,) int64.
+            Returns (wavs (B, T * hop) fp32 in [-1, 1] with zeros past n_samples, n_samples = lengths * hop (B,) int64).
+            The activations of the last stage are large (about 8 GB for one fp32 tensor at B = 256, T = 950), so the batch is
+            walked in sub-batches whose workspace -- six activation buffers of the largest stage plus the padded mel -- stays
+            under `max_workspace_bytes` (default 8 GB; one utterance at a time when even that does not fit).  The workspace is
+            kept and reused across calls; results do not depend on the split. '''
+        H.require_gpu(mel, lengths)
+        if mel.dim() != 3 or mel.shape[1] != self.num_mels:
+            raise ValueError(f'mel has shape {tuple(mel.shape)}, expected (B, {self.num_mels}, T)')
+        if lengths.dtype != torch.int64 or lengths.shape != (mel.shape[0],):
+            raise ValueError(f'lengths must be int64 of shape ({mel.shape[0]},)')
+        B, _, T = mel.shape
+        mel = mel.float()
+        lengths = lengths.clamp(0, T)
+        host = lengths.tolist()
+        wavs = torch.zeros((B, T * self.hop), dtype=torch.float32, device=mel.device)
+        with torch.cuda.device(mel.device):
+            b0 = 0
+            while b0 < B:
+                b1, t_sub = b0, 1
+                while b1 < B:                                             # greedy: as many utterances as fit under the cap
+                    t_new = max(t_sub, host[b1])
+                    most, mel_el = self._elements_per_utterance(t_new)
+                    if b1 > b0 and 4 * (b1 + 1 - b0) * (6 * most + mel_el) > max_workspace_bytes:
+                        break
+                    b1, t_sub = b1 + 1, t_new
+                self._run(mel[b0:b1], lengths[b0:b1].contiguous(), wavs[b0:b1], t_sub)
+                b0 = b1
+        return wavs, lengths * self.hop
