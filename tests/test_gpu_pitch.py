@@ -209,3 +209,37 @@ def test_extract_reference_parameters_end_to_end(fix, hp, tmp_path):
         outs.append(preds['utt_spk_3_ref_style'])
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
+
+
+def test_reference_parameters_of_a_mixed_rate_batch_equal_single_files(fix, hp, tmp_path):
+    ''' one `reference_parameters` call on four files: two at 16 kHz of different lengths with the shorter one first (a rate
+        group of ragged rows), one at the target rate (no resample), one at 44.1 kHz (a second resample launch).  In file
+        order short16, fast44, same22, long16 the rate groups, taken in order of rate, are the rows [0, 3], [2], [1]: the
+        16 kHz rows are not adjacent and the groups are not in file order.  Each file's arrays equal, bit for bit, what the
+        public pieces give for that file alone on its own one-row tensor. '''
+    from daft_exprt import audio
+    from daft_exprt import generate as G
+    from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
+    x16, x22 = fix.x[fix.index_at(16000)], fix.x[fix.index_at(22050)]
+    files = (('short16', 16000, x16[:2 * len(x16) // 3 + 1]), ('fast44', 44100, x22), ('same22', 22050, x22), ('long16', 16000, x16))
+    paths = []
+    for name, rate, x in files:
+        paths.append(str(tmp_path / f'{name}.wav'))
+        audio.write_wav_int16(paths[-1], rate, x)
+    assert hp.sampling_rate == 22050
+    got = G.reference_parameters(paths, hp)
+    assert len(got) == len(paths)
+    lengths = set()
+    for path, (energy, pitch, mel_spec) in zip(paths, got):
+        y, sr = audio.load_wav(path, sr=hp.sampling_rate)
+        assert sr == hp.sampling_rate
+        w, n = _to_device([y])
+        mel, en, nfr = mel_spectrogram_batch(w, n, hp)
+        lp, npf = pitch_batch(w, n, hp)
+        t = int(nfr[0])
+        assert t == int(npf[0]) == 1 + len(y) // hp.hop_length
+        assert np.array_equal(en[0, :t].cpu().numpy(), energy), path
+        assert np.array_equal(lp[0, :t].cpu().numpy(), pitch), path
+        assert np.array_equal(mel[0, :, :t].cpu().numpy(), mel_spec), path
+        lengths.add(len(y))
+    assert len(lengths) == 4                                             # every row of the batch has a length of its own

@@ -17,6 +17,7 @@ uses integer arithmetic (librosa: np.ceil of a float product).
 import functools
 import math
 import struct
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -152,10 +153,16 @@ def crop_range(sent_begin, sent_end, fs, n_samples):
     return (r.start, len(r)) if len(r) else (0, 0)
 
 
+def resampled_length(utt, fs):
+    ''' samples `utt` (`.samples`, `.rate`) holds at fs; a rate of fs keeps the count '''
+    return out_length(len(utt.samples), utt.rate, fs)
+
+
 def device_waves(utts, fs, device):
-    ''' utts: objects with `.samples` (mono float32 NumPy) and `.rate`.  Returns the (B, S) fp32 device waveforms at fs and
-        their lengths (host ints): one H2D copy and, for every source rate other than fs, one resample launch '''
-    n_total = [len(u.samples) if u.rate == fs else out_length(len(u.samples), u.rate, fs) for u in utts]
+    ''' utts: objects with `.samples` (mono float32 NumPy) and `.rate`.  Returns the (B, S) fp32 device waveforms at fs, zeros
+        past each length, and their lengths (host ints): one H2D copy per source rate and, for every one other than fs, one
+        resample launch '''
+    n_total = [resampled_length(u, fs) for u in utts]
     wavs = torch.zeros((len(utts), max(max(n_total), 1)), dtype=torch.float32, device=device)
     for rate in sorted(set(u.rate for u in utts)):
         rows = [b for b, u in enumerate(utts) if u.rate == rate]
@@ -228,11 +235,8 @@ def load_wav(path, sr=22050, device=None):
     y = to_float_mono(y)
     if sr is None or int(sr) == rate:
         return y, rate
-    dev = H.device(device)
-    x = torch.from_numpy(y).reshape(1, -1).to(dev)
-    n = torch.tensor([y.shape[0]], dtype=torch.int64, device=dev)
-    out, _ = resample_batch(x, n, rate, int(sr))
-    return out[0, :out_length(y.shape[0], rate, sr)].cpu().numpy(), int(sr)
+    wavs, n = device_waves([SimpleNamespace(samples=y, rate=rate)], int(sr), H.device(device))
+    return wavs[0, :n[0]].cpu().numpy(), int(sr)
 
 
 def rescale_wav_to_float32(x):

@@ -13,7 +13,7 @@ functions raise.
 feature files the trainer reads, a batch of utterances at a time: wavs, markers and sentences are read on one
 host thread, the batch is resampled, cropped (`dx_wav_crop`), analysed (`mel_spectrogram_batch`, `pitch_batch`), its aligner
 spans become frame counts (`dx_marker_durations`) and its frames symbol means (`dx_symbol_pool`), one copy brings everything
-to the host and another thread formats and writes the files.  `duration_to_integer`, `get_symbols_energy` and
+to the host and another thread (`write_behind.WriteBehind`) formats and writes the files.  `duration_to_integer`, `get_symbols_energy` and
 `get_symbols_pitch` are the one-utterance wrappers with the signatures of the reference; `update_markers`,
 `get_min_phone_duration` and `check_features_config_used` are host text logic.
 """
@@ -22,10 +22,8 @@ import json
 import logging
 import math
 import os
-import queue
 import re
 import string
-import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -33,8 +31,9 @@ import numpy as np
 import torch
 
 from daft_exprt import _hip as H
-from daft_exprt.audio import crop_range, device_waves, fft_tables, out_length, read_wav, to_float_mono
+from daft_exprt.audio import crop_range, device_waves, fft_tables, read_wav, resampled_length, to_float_mono
 from daft_exprt.audio import rescale_wav_to_float32  # noqa: F401  (the reference keeps it here, `extract_features.py:362`)
+from daft_exprt.write_behind import WriteBehind
 from daft_exprt.symbols import SIL_WORD_SYMBOL, eos, punctuation, whitespace
 
 _logger = logging.getLogger(__name__)
@@ -225,6 +224,11 @@ def get_min_phone_duration(lines, min_phone_dur=1000.):
     return min_phone_dur
 
 
+def marker_lines_span(lines):
+    ''' (sent_begin, sent_end) in seconds of the rows of a .markers file: begin of the first row, end of the last '''
+    return float(lines[0].strip().split(sep='\t')[0]), float(lines[-1].strip().split(sep='\t')[1])
+
+
 def wav_crop_batch(wavs, crop, width):
     ''' `dx_wav_crop`: wavs (B, S) fp32 and crop (B, 2) int64 (begin, length) on the device -> (B, width) fp32, row b holding
         wavs[b, begin_b: begin_b + length_b] left-aligned and zeros behind it '''
@@ -394,8 +398,8 @@ class _FeatureUtterance(object):
     ''' what the reader thread hands over for one utterance '''
     def __init__(self, speaker, name, lines, sentence):
         self.speaker, self.name, self.lines, self.sentence, self.samples, self.rate = speaker, name, lines, sentence, None, None
+        self.sent_begin, self.sent_end = marker_lines_span(lines)
         rows = [line.strip().split(sep='\t') for line in lines]
-        self.sent_begin, self.sent_end = float(rows[0][0]), float(rows[-1][1])
         self.spans = [[float(row[0]) - self.sent_begin, float(row[1]) - self.sent_begin] for row in rows]
 
 
@@ -428,38 +432,15 @@ def _read_features_batch(dataset_dir, speaker, names, hparams, skipped):
     return utts
 
 
-class _FeatureWriter(object):
-    ''' formats and writes the batches on a thread of its own; the first unexpected error is re-raised by `put` / `close` '''
+class _FeatureFiles(object):
+    ''' `write` of the pass's `WriteBehind`: formats and writes the files of one batch; counts `written`, appends to `skipped` '''
     STATUS = {1: 'the markers end before the frames do', 2: 'a marker of zero length',
               3: 'the frame durations do not match the markers or the mel-spectrogram'}
 
     def __init__(self, features_dir, hparams, skipped):
-        self.features_dir, self.hparams, self.skipped = features_dir, hparams, skipped
-        self.q = queue.Queue(maxsize=4)
-        self.error, self.written, self.busy_s = None, 0, 0.
-        self.thread = threading.Thread(target=self._run, name='features_writer', daemon=True)
-        self.thread.start()
+        self.features_dir, self.hparams, self.skipped, self.written = features_dir, hparams, skipped, 0
 
-    def put(self, job):
-        if self.error is not None:
-            raise self.error
-        self.q.put(job)
-
-    def _run(self):
-        while True:
-            job = self.q.get()
-            if job is None:
-                return
-            if self.error is None:
-                try:
-                    self._write(*job)
-                except Exception as e:        # surfaced by put / close
-                    self.error = e
-
-    def _write(self, event, host, layout, utts):
-        event.synchronize()
-        t0 = time.time()
-        raw = host.numpy()
+    def __call__(self, raw, layout, utts):
         parts, off = {}, 0
         for key, dtype, shape in layout:
             size = int(np.prod(shape)) * np.dtype(dtype).itemsize
@@ -492,13 +473,6 @@ class _FeatureWriter(object):
                 with open(base + ext, 'w', encoding='utf-8') as f:
                     f.write(text)
             self.written += 1
-        self.busy_s += time.time() - t0
-
-    def close(self):
-        self.q.put(None)
-        self.thread.join()
-        if self.error is not None:
-            raise self.error
 
 
 def features_batch(utts, hparams, device):
@@ -579,7 +553,8 @@ def extract_features(dataset_dir, features_dir, hparams, n_jobs, batch_size=64, 
             wav_files = [os.path.join(wavs_dir, f'{name}.wav') for name in missing]
             sizes = [os.path.getsize(path) // 2 if os.path.isfile(path) else 0 for path in wav_files]
             batches = _plan_batches(missing, sizes, int(batch_size), int(sample_budget))
-            writer = _FeatureWriter(features_dir, hparams, skipped)
+            files = _FeatureFiles(features_dir, hparams, skipped)
+            writer = WriteBehind(files, 'features_writer')
             reader = ThreadPoolExecutor(max_workers=1, thread_name_prefix='features_reader')
             try:
                 pending = reader.submit(_read_features_batch, dataset_dir, speaker, batches[0], hparams, skipped)
@@ -591,8 +566,7 @@ def extract_features(dataset_dir, features_dir, hparams, n_jobs, batch_size=64, 
                         pending = reader.submit(_read_features_batch, dataset_dir, speaker, batches[idx + 1], hparams, skipped)
                     keep = []
                     for u in utts:                   # the mel front-end reflects half a window at both ends of the crop
-                        n_total = len(u.samples) if u.rate == fs else out_length(len(u.samples), u.rate, fs)
-                        if crop_range(u.sent_begin, u.sent_end, fs, n_total)[1] < min_samples:
+                        if crop_range(u.sent_begin, u.sent_end, fs, resampled_length(u, fs))[1] < min_samples:
                             _logger.warning(f'Ignoring {speaker} -- {u.name} -- the wav ends before its markers do')
                             skipped.append((speaker, u.name, 'the wav ends before its markers do'))
                         else:
@@ -600,16 +574,12 @@ def extract_features(dataset_dir, features_dir, hparams, n_jobs, batch_size=64, 
                     if not keep:
                         continue
                     buf, layout = features_batch(keep, hparams, dev)
-                    host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
-                    host.copy_(buf, non_blocking=True)
-                    event = torch.cuda.Event()
-                    event.record()
-                    writer.put((event, host, layout, keep))
+                    writer.put(buf, layout, keep)
                     report['batches'] += 1
             finally:
                 reader.shutdown(wait=True)
                 writer.close()
-                report['written'] += writer.written
+                report['written'] += files.written
                 report['write_s'] += writer.busy_s
         # the config the features were extracted with
         hparams.save_hyper_params(os.path.join(spk_features_dir, 'config.json'))

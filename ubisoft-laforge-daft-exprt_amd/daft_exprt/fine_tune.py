@@ -8,8 +8,8 @@ least one second, `<file>.npy` (the float32 (n_mel, T) mel prediction) and `<fil
 
 Per batch the device work is the eval forward, one `dx_resample` launch per source rate other than `sampling_rate`
 (the reference's `librosa.load(..., sr=hparams.sampling_rate)`), one `dx_ft_pack` (crop + int16) and one device-to-host
-copy.  The batch's wav files are read on a host thread while the forward runs, and the files are written on another thread,
-so the next batch's forward never waits for file output.
+copy.  The batch's wav files are read on a host thread while the forward runs, and the files are written on another thread
+(`write_behind.WriteBehind`), so the next batch's forward never waits for file output.
 
 Differences from the reference, by design:
   * the target mel the reference computes only to compare its shape with the prediction's (`fine_tune.py:101-104`) is not
@@ -21,20 +21,18 @@ import argparse
 import json
 import logging
 import os
-import queue
-import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from daft_exprt.audio import crop_range, ft_pack, read_wav, to_float_mono, write_wav_int16
-from daft_exprt.audio import device_waves as _device_waves
+from daft_exprt.audio import crop_range, device_waves, ft_pack, read_wav, to_float_mono, write_wav_int16
 from daft_exprt.data_loader import prepare_data_loaders
-from daft_exprt.extract_features import nb_frames
+from daft_exprt.extract_features import marker_lines_span, nb_frames
 from daft_exprt.hparams import HyperParams
 from daft_exprt.model import DaftExprt
+from daft_exprt.write_behind import WriteBehind
 
 _logger = logging.getLogger(__name__)
 
@@ -50,8 +48,7 @@ def speaker_of(feature_dir, feature_file, speakers):
 def markers_span(markers_file):
     ''' (sent_begin, sent_end) in seconds: begin of the first row, end of the last (`fine_tune.py:96-99`) '''
     with open(markers_file, 'r', encoding='utf-8') as f:
-        lines = f.readlines()
-    return float(lines[0].strip().split(sep='\t')[0]), float(lines[-1].strip().split(sep='\t')[1])
+        return marker_lines_span(f.readlines())
 
 
 class _Utterance(object):
@@ -72,35 +69,13 @@ def _read_batch(hparams, feature_dirs, feature_files):
     return out
 
 
-class _Writer(object):
-    ''' writes the packed batches on a thread of its own; the first unexpected error is re-raised by `close` '''
+class _PackedFiles(object):
+    ''' `write` of the pass's `WriteBehind`: the .npy and .wav of every utterance of one packed batch; counts `written` / `skipped` '''
     def __init__(self, hparams, ft_data_set):
         self.fs, self.n_mel, self.root = int(hparams.sampling_rate), int(hparams.n_mel_channels), ft_data_set
-        self.q = queue.Queue(maxsize=4)
-        self.error, self.written, self.skipped, self.busy_s = None, 0, 0, 0.
-        self.thread = threading.Thread(target=self._run, name='fine_tune_writer', daemon=True)
-        self.thread.start()
+        self.written, self.skipped = 0, 0
 
-    def put(self, job):
-        if self.error is not None:
-            raise self.error
-        self.q.put(job)
-
-    def _run(self):
-        while True:
-            job = self.q.get()
-            if job is None:
-                return
-            if self.error is None:
-                try:
-                    self._write(*job)
-                except Exception as e:        # surfaced by put / close
-                    self.error = e
-
-    def _write(self, event, host, utts, crops, lengths):
-        event.synchronize()
-        t0 = time.time()
-        raw = host.numpy()
+    def __call__(self, raw, utts, crops, lengths):
         mel_off, wav_off = 0, 4 * self.n_mel * sum(lengths)
         for u, (_, n), T in zip(utts, crops, lengths):
             mel = raw[mel_off: mel_off + 4 * self.n_mel * T].view(np.float32).reshape(self.n_mel, T)
@@ -121,13 +96,6 @@ class _Writer(object):
                 for path in (mel_file, wav_file):
                     if os.path.isfile(path):
                         os.remove(path)
-        self.busy_s += time.time() - t0
-
-    def close(self):
-        self.q.put(None)
-        self.thread.join()
-        if self.error is not None:
-            raise self.error
 
 
 def fine_tuning(hparams):
@@ -152,7 +120,8 @@ def fine_tuning(hparams):
     fs, n_mel = int(hparams.sampling_rate), int(hparams.n_mel_channels)
     model.eval()
     start, read_wait, n_utts = time.time(), 0., 0
-    writer = _Writer(hparams, ft_data_set)
+    files = _PackedFiles(hparams, ft_data_set)
+    writer = WriteBehind(files, 'fine_tune_writer')
     reader = ThreadPoolExecutor(max_workers=1, thread_name_prefix='fine_tune_reader')
     try:
         with torch.no_grad():
@@ -163,7 +132,7 @@ def fine_tuning(hparams):
                 t0 = time.time()
                 utts = pending.result()
                 read_wait += time.time() - t0
-                wavs, n_total = _device_waves(utts, fs, dev)
+                wavs, n_total = device_waves(utts, fs, dev)
                 lengths = [int(t) for t in batch[9]]
                 crops = [crop_range(u.span[0], u.span[1], fs, n) for u, n in zip(utts, n_total)]
                 for u, (_, n), T in zip(utts, crops, lengths):
@@ -172,11 +141,7 @@ def fine_tuning(hparams):
                                          f'frames, the mel prediction has {T}')
                 crop = torch.tensor(crops, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
                 buf = ft_pack(mel_specs, output_lengths, wavs, crop, n_mel * sum(lengths), sum(n for _, n in crops))
-                host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=True)
-                host.copy_(buf, non_blocking=True)
-                event = torch.cuda.Event()
-                event.record()
-                writer.put((event, host, utts, crops, lengths))
+                writer.put(buf, utts, crops, lengths)
                 n_utts += len(utts)
                 if idx % 10 == 0 or idx == len(train_loader) - 1:
                     _logger.info(f'fine-tuning data set: batch {idx + 1} / {len(train_loader)}, {n_utts} utterances, '
@@ -185,7 +150,7 @@ def fine_tuning(hparams):
         reader.shutdown(wait=True)
         writer.close()
     torch.cuda.synchronize()
-    return {'utterances': n_utts, 'written': writer.written, 'skipped': writer.skipped, 'seconds': time.time() - start,
+    return {'utterances': n_utts, 'written': files.written, 'skipped': files.skipped, 'seconds': time.time() - start,
             'read_wait_s': read_wait, 'write_s': writer.busy_s}
 
 

@@ -12,9 +12,15 @@ a list of words (lists of phone symbols) and boundary symbols, exactly what `pre
 import logging
 import os
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
+
+from daft_exprt import _hip as H
+from daft_exprt import audio, evaluate, griffin_lim
+from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
+from daft_exprt.vocoder import pcm16
 
 _logger = logging.getLogger(__name__)
 
@@ -111,7 +117,8 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         decoder's mel, made on the device before the copy to the host and written as 16-bit PCM (`audio.write_wav_int16`,
         `n_frames * hop` samples); `use_griffin_lim` is not needed and no preview is made; `scores` are computed on the vocoder's
         audio.  With None nothing changes. '''
-    if scores is not None and not use_griffin_lim and vocoder is None:
+    source = 'vocoder' if vocoder is not None else 'griffin_lim' if use_griffin_lim else None
+    if scores is not None and source is None:
         raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
     for idx, file_name in enumerate(batch_file_names):
         file_name += f'_spk_{batch_speaker_ids[idx]}'
@@ -131,17 +138,15 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
     inputs = tuple(t.to(gpu, non_blocking=True) for t in col[:-1])
     inference = model.inference if hasattr(model, 'inference') else model.module.inference   # DDP-wrapped callers (270-278)
     encoder_preds, decoder_preds, alignments = inference(inputs, pitch_transform, hparams)
-    if vocoder is not None:
-        from daft_exprt.vocoder import pcm16
+    if source == 'vocoder':              # HiFi-GAN audio, written as 16-bit PCM
         vocoder.check_hparams(hparams)
         wavs, n_samples = vocoder(decoder_preds[0].float().contiguous(), decoder_preds[1])
-        pcm = pcm16(wavs)
-    elif use_griffin_lim:
-        from daft_exprt import griffin_lim
+        samples, write = pcm16(wavs), audio.write_wav_int16
+    elif source == 'griffin_lim':        # the Griffin-Lim preview, written as 64-bit float
         wavs, n_samples = griffin_lim.griffin_lim_batch(decoder_preds[0].float().contiguous(), decoder_preds[1], hparams)
-    if vocoder is not None or use_griffin_lim:
+        samples, write = wavs, audio.write_wav
+    if source is not None:
         if scores is not None:
-            from daft_exprt import evaluate
             batch_scores = evaluate.prosody_transfer_scores(wavs, n_samples, inputs[6], inputs[5], inputs[8], hparams)
     duration, duration_int, energy, pitch, input_lengths = (t.detach().cpu().numpy() for t in encoder_preds)
     mel_spec, output_lengths = (t.detach().cpu().numpy() for t in decoder_preds)
@@ -153,16 +158,10 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         np.savez(os.path.join(output_dir, f'{name}.npz'), mel_spec=mel_spec[i, :, :t])
         predictions[f'{name}'] = [duration[i, :l], duration_int[i, :l], energy[i, :l], pitch[i, :l], mel_spec[i, :, :t],
                                   weights[i, :l, :t]]
-    if vocoder is not None:
-        from daft_exprt import audio
-        pcm, n_samples = pcm.cpu().numpy(), n_samples.cpu().numpy()
+    if source is not None:
+        samples, n_samples = samples.cpu().numpy(), n_samples.cpu().numpy()
         for i, name in enumerate(file_names):
-            audio.write_wav_int16(os.path.join(output_dir, f'{name}.wav'), hparams.sampling_rate, pcm[i, :int(n_samples[i])])
-    elif use_griffin_lim:
-        wavs, n_samples = wavs.cpu().numpy(), n_samples.cpu().numpy()
-        for i, name in enumerate(file_names):
-            griffin_lim.write_wav(os.path.join(output_dir, f'{name}.wav'), hparams.sampling_rate, wavs[i, :int(n_samples[i])])
-    if vocoder is not None or use_griffin_lim:
+            write(os.path.join(output_dir, f'{name}.wav'), hparams.sampling_rate, samples[i, :int(n_samples[i])])
         if scores is not None:
             host = {key: t.cpu().tolist() for key, t in batch_scores.items()}
             for i, name in enumerate(file_names):
@@ -171,20 +170,15 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
     return predictions
 
 
-def _parameters_of(wavs, hparams, device):
-    ''' [(energy (T,), pitch (T,), mel_spec (n_mel, T)) NumPy] of float32 waveforms (a list) sampled at hparams.sampling_rate:
-        one `pitch_batch` and one `mel_spectrogram_batch` over the right-padded batch '''
-    from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
-    lengths = [int(w.shape[0]) for w in wavs]
-    x = torch.zeros((len(wavs), max(lengths)), dtype=torch.float32)
-    for i, w in enumerate(wavs):
-        x[i, :lengths[i]] = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
-    x, n = x.to(device), torch.tensor(lengths, dtype=torch.int64, device=device)
-    pitch, n_pitch = pitch_batch(x, n, hparams)
-    mel, energy, n_mel = mel_spectrogram_batch(x, n, hparams)
+def _parameters_of(wavs, lengths, hparams):
+    ''' [(energy (T,), pitch (T,), mel_spec (n_mel, T)) NumPy] of the (B, S) fp32 device waveforms `wavs` at
+        hparams.sampling_rate, zeros past their `lengths` (host ints): one `pitch_batch` and one `mel_spectrogram_batch` '''
+    n = torch.tensor(lengths, dtype=torch.int64, device=wavs.device)
+    pitch, n_pitch = pitch_batch(wavs, n, hparams)
+    mel, energy, n_mel = mel_spectrogram_batch(wavs, n, hparams)
     pitch, energy, mel, n_pitch, n_mel = (t.cpu().numpy() for t in (pitch, energy, mel, n_pitch, n_mel))
     out = []
-    for i in range(len(wavs)):
+    for i in range(len(lengths)):
         t = int(n_mel[i])
         assert int(n_pitch[i]) == t, f'{int(n_pitch[i])} -- {t}'            # `generate.py:459`
         out.append((energy[i, :t].copy(), pitch[i, :t].copy(), mel[i, :, :t].copy()))
@@ -192,32 +186,15 @@ def _parameters_of(wavs, hparams, device):
 
 
 def reference_parameters(audio_refs, hparams, device=None):
-    ''' [(energy, pitch, mel_spec)] of wav files, in order.  Files are read on the host (`audio.read_wav`), resampled to
-        hparams.sampling_rate on the device in one launch per source rate, then tracked and analysed as one batch. '''
-    from daft_exprt import _hip as H
-    from daft_exprt import audio
-    dev = H.device(device)
-    sr = int(hparams.sampling_rate)
-    loaded = []
+    ''' [(energy, pitch, mel_spec)] of wav files, in order.  Files are read on the host (`audio.read_wav`), brought to
+        hparams.sampling_rate on the device (`audio.device_waves`: one launch per source rate), then tracked and analysed there
+        as one batch. '''
+    utts = []
     for path in audio_refs:
         y, rate = audio.read_wav(path)
-        loaded.append((audio.to_float_mono(y), rate))
-    wavs = [None] * len(loaded)
-    for rate in sorted({r for _, r in loaded}):
-        idx = [i for i, (_, r) in enumerate(loaded) if r == rate]
-        if rate == sr:
-            for i in idx:
-                wavs[i] = loaded[i][0]
-            continue
-        lengths = [loaded[i][0].shape[0] for i in idx]
-        x = torch.zeros((len(idx), max(lengths)), dtype=torch.float32)
-        for row, i in enumerate(idx):
-            x[row, :lengths[row]] = torch.from_numpy(loaded[i][0])
-        y, _ = audio.resample_batch(x.to(dev), torch.tensor(lengths, dtype=torch.int64, device=dev), rate, sr)
-        y = y.cpu().numpy()
-        for row, i in enumerate(idx):
-            wavs[i] = y[row, :audio.out_length(lengths[row], rate, sr)]
-    return _parameters_of(wavs, hparams, dev)
+        utts.append(SimpleNamespace(samples=audio.to_float_mono(y), rate=rate))
+    wavs, lengths = audio.device_waves(utts, int(hparams.sampling_rate), H.device(device))
+    return _parameters_of(wavs, lengths, hparams)
 
 
 def _ref_file(audio_ref, output_dir):
@@ -227,23 +204,14 @@ def _ref_file(audio_ref, output_dir):
 def extract_reference_parameters(audio_ref, output_dir, hparams, device=None):
     ''' `generate.py:440-462`, same contract: `<output_dir>/<name of audio_ref without .wav>.npz` with keys `energy`, `pitch`
         (log Hz per mel frame, 0 where unvoiced) and `mel_spec`, all of the same number of frames; nothing is done when the
-        file already exists.  Built from `audio.load_wav` (resampling on the device when the file's rate differs),
-        `pitch_batch` and `mel_spectrogram_batch`; the energy is the front-end's own (the norm of exp(mel) over the channels,
-        what `extract_energy(np.exp(mel_spec))` computes). '''
-    from daft_exprt import _hip as H
-    from daft_exprt import audio
-    os.makedirs(output_dir, exist_ok=True)
-    ref_file = _ref_file(audio_ref, output_dir)
-    if not os.path.isfile(ref_file):
-        dev = H.device(device)
-        wav, _ = audio.load_wav(audio_ref, sr=hparams.sampling_rate, device=dev)
-        energy, pitch, mel_spec = _parameters_of([wav], hparams, dev)[0]
-        np.savez(ref_file, energy=energy, pitch=pitch, mel_spec=mel_spec)
+        file already exists.  The batch form with one file: the energy is the front-end's own (the norm of exp(mel) over the
+        channels, what `extract_energy(np.exp(mel_spec))` computes). '''
+    extract_reference_parameters_batch([audio_ref], output_dir, hparams, device)
 
 
 def extract_reference_parameters_batch(audio_refs, output_dir, hparams, device=None):
     ''' `extract_reference_parameters` for a whole style bank: the files that have no `.npz` yet go through one resampling
-        launch per source rate, one pitch track and one mel front-end call together '''
+        launch per source rate, one pitch track and one mel front-end call together (`reference_parameters`) '''
     os.makedirs(output_dir, exist_ok=True)
     todo = [ref for ref in audio_refs if not os.path.isfile(_ref_file(ref, output_dir))]
     todo = list(dict.fromkeys(todo))
