@@ -702,6 +702,49 @@ int dx_voc_upsample(const float* x, long ldx, const void* w_packed, int w_dtype,
 int dx_voc_post(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, const int64_t* n_rows, int B, int N,
                 int C, int taps, float in_slope, void* stream);
 
+/* ---- K25: copy-synthesis scores -- mel-cepstral distortion, F0 error and voicing error between a recording and a synthesis of
+ * the same text, along the path of a dynamic time warping of their mel cepstra.  Additive entry points (the ABI version stays).
+ * Per pair, independently of the other pairs: nothing at or past n_ref[b] / n_gen[b] is read, and a pair gives the same bits alone,
+ * in any batch, with any padded extent and whatever the workspace held.  No atomics.
+ *
+ * dx_mel_cepstrum: mel (B, n_mel, T) fp32 (natural-log mel; utterances ld_b, channels ld_m floats apart) with n[b] <= T frames ->
+ * cep (B, T, K) fp32, time-major, contiguous: cep[b, t, k] = sum_m dct[k, m] * mel[b, m, t] for t < n[b], zeros for n[b] <= t < T.
+ * dct (K, n_mel) fp32 is the caller's table: rows 1 .. K of the orthonormal DCT-II, sqrt(2 / n_mel) cos(pi (m + 1/2) k / n_mel),
+ * computed in double and rounded once (c0, the level, is dropped).  1 <= K < n_mel: DX_ERR_SHAPE otherwise; K * n_mel > 4096 (the
+ * table is staged in LDS): DX_ERR_UNSUPPORTED.  The sum runs in order of m, fused multiply-adds in fp32.
+ *
+ * dx_dtw_align: the unconstrained DTW (no band, no slope weight) of cep_ref[b, :n_ref[b]] against cep_gen[b, :n_gen[b]], both
+ * (B, T, K) fp32 contiguous, with
+ *   d(i, j) = sqrt(sum_k (ref[i, k] - gen[j, k])^2)   in fp32, terms in order of k, computed on the fly (no cost matrix in memory),
+ *   D(i, j) = d(i, j) + min(D(i - 1, j - 1), D(i - 1, j), D(i, j - 1)),  D(0, 0) = d(0, 0),
+ * the predecessor being the FIRST minimum in the order diagonal, (i - 1, j), (i, j - 1): a later candidate replaces an earlier one
+ * only when strictly smaller.  total[b] = D(n_ref - 1, n_gen - 1); path (B, T_ref + T_gen - 1, 2) int32: the cells (i, j) from
+ * (0, 0) to (n_ref - 1, n_gen - 1), entries at or past path_len[b] are -1.  n_ref[b] == 0 or n_gen[b] == 0: path_len 0, total NaN.
+ * ws: ws_stride bytes per pair of scratch, ws_stride >= T_ref * ceil(T_gen / 4) (2 bits per cell: 4 MiB per pair at the limit);
+ * nothing in it has to be initialised or to survive the call.  The backtrack takes at most n_ref + n_gen - 1 steps and its move is
+ * forced at i = 0 and at j = 0, so no workspace content and no non-finite cepstrum can walk it out of the matrix or make it loop
+ * (non-finite values inside the live region are the caller's error: the path stays monotone, the totals are non-finite).
+ * One workgroup per pair, three anti-diagonals of D in LDS (53 252 B with the code bytes in progress): T_ref, T_gen >
+ * dx_dtw_max_len() = 4096 returns DX_ERR_UNSUPPORTED before any launch.
+ *
+ * dx_dtw_path_scores: per pair, over the entries p < path_len[b] of `path` (laid out as dx_dtw_align writes it for the same
+ * T_ref, T_gen; an entry that is no cell of the pair is skipped and not counted), sums in double in an order fixed by path_len:
+ *   mcd_db[b]        = (10 sqrt(2) / ln 10) * mean d(i, j)                                   NaN for an empty path
+ *   f0_rmse_cents[b] = sqrt(mean((1200 / ln 2 * (lp_ref[b, i] - lp_gen[b, j]))^2)) over the entries with both values > 0 (log Hz,
+ *                      <= 0 is unvoiced); NaN when there is none
+ *   vuv_error[b]     = the share of entries where exactly one side is voiced;              NaN for an empty path
+ *   voiced_pairs[b]  = the entries with both sides voiced;   used_len[b] = the entries counted.
+ * lp_ref (B, ld_lpr) / lp_gen (B, ld_lpg) fp32 may both be NULL: f0_rmse_cents and vuv_error are then NaN, voiced_pairs 0. */
+long dx_dtw_max_len(void);
+int dx_mel_cepstrum(const float* mel, long ld_b, long ld_m, const int64_t* n, const float* dct, float* cep, int B, int n_mel,
+                    int T, int K, void* stream);
+int dx_dtw_align(const float* cep_ref, const int64_t* n_ref, const float* cep_gen, const int64_t* n_gen, float* total,
+                 int* path, int* path_len, void* ws, long ws_stride, int B, int T_ref, int T_gen, int K, void* stream);
+int dx_dtw_path_scores(const float* cep_ref, const int64_t* n_ref, const float* cep_gen, const int64_t* n_gen, const int* path,
+                       const int* path_len, const float* lp_ref, long ld_lpr, const float* lp_gen, long ld_lpg, float* mcd_db,
+                       float* f0_rmse_cents, float* vuv_error, int* voiced_pairs, int* used_len, int B, int T_ref, int T_gen,
+                       int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,125 @@
+#!/usr/bin/env python
+"""Copy-synthesis scores of a checkpoint against held-out recordings of the same text:
+    python scripts/evaluate.py -chk CHECKPOINT -vf FILE_LIST -out OUT_DIR [-bs 50] [-voc G_CKPT [-vcfg JSON]] [-n MAX_UTTERANCES] [-nc 13]
+
+  -chk  training checkpoint: weights, hyper-parameters and speaker statistics, as for `scripts/synthesize.py`
+  -vf   a `features_dir|feature_file|speaker_id` list, e.g. the validation list `scripts/pre_process.py` writes; read through
+        `DaftExprtDataLoader` and its collate, in the list's order
+  -voc  a HiFi-GAN generator checkpoint (-vcfg its `config.json`, default: the one beside it): the `audio` level scores its
+        waveform instead of the Griffin-Lim preview
+  -n    score the first N utterances of the list only
+  -nc   cepstral coefficients 1..K of the distortion (default 13)
+
+Every utterance is synthesised free-running -- predicted durations, predicted prosody, decoder -- with its own recording as the
+prosody reference and its own speaker, and compared with that recording after dynamic time warping (`daft_exprt/evaluate.py`,
+`copy_synthesis_scores`).  `<out>/copy_synthesis.json` holds, per file, the speaker id and the scores at two levels -- `mel`: the
+decoder's mel against the recorded mel (MCD, frame counts); `audio`: the vocoder's or Griffin-Lim's waveform analysed again
+(MCD, F0 RMSE in cents, voicing error, voiced pairs, path length, frame counts); NaN is written as null -- and a `summary`: per
+level and key the mean, the median and the count of the finite values, over all files and per speaker."""
+import argparse
+import json
+import logging
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'ubisoft-laforge-daft-exprt_amd')
+sys.path.insert(0, PKG)
+
+_logger = logging.getLogger('evaluate')
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description='Score the free-running synthesis of a checkpoint against recordings of the same text')
+    parser.add_argument('-chk', '--checkpoint', required=True, help='training checkpoint (weights, hyper-parameters, statistics)')
+    parser.add_argument('-vf', '--validation_files', required=True, help='list of features_dir|feature_file|speaker_id lines')
+    parser.add_argument('-out', '--output_dir', required=True, help='where copy_synthesis.json goes')
+    parser.add_argument('-bs', '--batch_size', type=int, default=50, help='utterances per inference call')
+    parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN generator checkpoint: score its audio instead of the Griffin-Lim preview')
+    parser.add_argument('-vcfg', '--vocoder_config', default=None, help='HiFi-GAN config.json (default: beside the vocoder checkpoint)')
+    parser.add_argument('-n', '--max_utterances', type=int, default=None, help='score the first N utterances of the list only')
+    parser.add_argument('-nc', '--n_coeffs', type=int, default=13, help='cepstral coefficients 1..K of the distortion')
+    return parser.parse_args(argv)
+
+
+def score_files(model, hparams, list_file, batch_size, vocoder=None, max_utterances=None, n_coeffs=13):
+    ''' {file: {'speaker_id': id, 'mel': {key: value}, 'audio': {key: value}}} in the list's order; floats may be NaN '''
+    from daft_exprt.data_loader import DaftExprtDataCollate, DaftExprtDataLoader
+    from daft_exprt.evaluate import COPY_LEVELS, DTW_KEYS, copy_synthesis_scores
+    dataset = DaftExprtDataLoader(list_file, hparams, shuffle=False)
+    collate = DaftExprtDataCollate(hparams)
+    count = len(dataset) if max_utterances is None else min(len(dataset), max(0, max_utterances))
+    records = {}
+    for start in range(0, count, batch_size):
+        batch = collate([dataset[i] for i in range(start, min(count, start + batch_size))])
+        scores = copy_synthesis_scores(model, batch, hparams, vocoder=vocoder, n_coeffs=n_coeffs)
+        host = {level: {key: scores[level][key].cpu().tolist() for key in DTW_KEYS} for level in COPY_LEVELS}
+        for row, (features_dir, feature_file) in enumerate(zip(batch[11], batch[12])):
+            name = f'{os.path.basename(os.path.normpath(features_dir))}/{feature_file}'
+            records[name] = {'speaker_id': int(batch[10][row]),
+                             **{level: {key: host[level][key][row] for key in DTW_KEYS} for level in COPY_LEVELS}}
+    order = {f'{os.path.basename(os.path.normpath(line[0]))}/{line[1]}': i for i, line in enumerate(dataset.data)}
+    return dict(sorted(records.items(), key=lambda item: order[item[0]]))
+
+
+def _stats(values):
+    finite = [float(v) for v in values if v is not None and math.isfinite(v)]
+    return {'mean': statistics.fmean(finite) if finite else None, 'median': statistics.median(finite) if finite else None,
+            'count': len(finite)}
+
+
+def summarise(records, levels, keys):
+    ''' per level and key the mean, median and count of the finite values: over all files, and per speaker '''
+    def table(entries):
+        return {level: {key: _stats([e[level][key] for e in entries]) for key in keys} for level in levels}
+    summary = {'files': len(records), **table(list(records.values())), 'speakers': {}}
+    for speaker in sorted({e['speaker_id'] for e in records.values()}):
+        mine = [e for e in records.values() if e['speaker_id'] == speaker]
+        summary['speakers'][str(speaker)] = {'files': len(mine), **table(mine)}
+    return summary
+
+
+def write_report(output_dir, records, audio, levels, keys):
+    ''' `<out>/copy_synthesis.json`: {'audio': which waveform was scored, 'files': records, 'summary': ...}; NaN becomes null '''
+    def clean(v):
+        return None if isinstance(v, float) and not math.isfinite(v) else v
+    files = {name: {'speaker_id': e['speaker_id'], **{level: {k: clean(v) for k, v in e[level].items()} for level in levels}}
+             for name, e in records.items()}
+    report = {'audio': audio, 'files': files, 'summary': summarise(files, levels, keys)}
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, 'copy_synthesis.json')
+    with open(path, 'w', encoding='utf-8') as f:
+        json.dump(report, f, indent=1)
+    for level in levels:
+        for key in ('mcd_db', 'f0_rmse_cents', 'vuv_error'):
+            s = report['summary'][level][key]
+            if s['count']:
+                _logger.info(f'{level} {key}: mean {s["mean"]:.3f}, median {s["median"]:.3f} over {s["count"]} of {len(files)} files')
+            else:
+                _logger.info(f'{level} {key}: undefined for all {len(files)} files')
+    _logger.info(f'Copy-synthesis scores written to {path}')
+    return report
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    logging.basicConfig(format='%(asctime)s [%(levelname)s] %(message)s', datefmt='%Y-%m-%d %H:%M:%S', level=logging.INFO)
+    for what, path in (('checkpoint', args.checkpoint), ('file list', args.validation_files), ('vocoder checkpoint', args.vocoder)):
+        if path is not None and not os.path.isfile(path):
+            raise SystemExit(f'evaluate.py: no such {what}: {path}')
+    if args.batch_size < 1:
+        raise SystemExit(f'evaluate.py: -bs {args.batch_size}: at least one utterance per batch')
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from synthesize import load_model, load_vocoder
+    from daft_exprt.evaluate import COPY_LEVELS, DTW_KEYS
+    model, hparams = load_model(args.checkpoint)
+    vocoder = load_vocoder(args.vocoder, args.vocoder_config, hparams) if args.vocoder else None
+    records = score_files(model, hparams, args.validation_files, args.batch_size, vocoder, args.max_utterances, args.n_coeffs)
+    write_report(args.output_dir, records, 'hifi-gan' if vocoder is not None else 'griffin-lim', COPY_LEVELS, DTW_KEYS)
+
+
+if __name__ == '__main__':
+    main()
