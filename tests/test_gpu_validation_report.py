@@ -135,6 +135,23 @@ def test_alignment_scores_across_waves():
     assert (hits > 0).all() and (hits < frames).all()
 
 
+def test_alignment_scores_carry_the_prefix_into_a_second_chunk():
+    ''' the kernel scans 256 symbols per chunk: symbols 256 .. 259 get their first frame from the carry of the chunk before.
+        Durations of 0 .. 2 sum to about L = 260, below T = 300, so it is utterance 0's own out_length that its sum passes:
+        the cut falls inside symbol 258, in the second chunk.  Utterance 1 ends on the second chunk's first symbol. '''
+    B, L, T = 2, 260, 300
+    durations = np.random.default_rng(31).integers(0, 3, size=(B, L))
+    durations[0, 256:] = [1, 0, 2, 2]
+    durations[1, 256] = 2
+    in_lengths = [260, 257]
+    out_lengths = [int(durations[0, :256].sum()) + 2, 300]
+    assert durations[0, :256].sum() < out_lengths[0] < durations[0].sum() and durations[1, :257].sum() <= 300
+    w = _softmax_weights(durations, in_lengths, out_lengths, L, T, seed=32)
+    frames, hits, _ = _check_alignment(w, durations, in_lengths, out_lengths)
+    assert frames.tolist() == [out_lengths[0], int(durations[1, :257].sum())]
+    assert (hits > 0).all() and (hits < frames).all()
+
+
 def test_validate_with_a_report_matches_the_oracle(tmp_path):
     ''' 2-block, 2-speaker model, two batches of 3 utterances with T <= 64: the written report equals the oracle applied to the same
         model outputs fetched to the host, and the losses are those of `validate` without a report, bit for bit '''

@@ -27,7 +27,10 @@ constexpr int FLAT_BLOCK = 4096;
 
 struct AdamHyper { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
+// dx_block_sum<4, false> as far as thread 0, the one reader, can tell: lane 0 of a wave adds the same pairs in the same order
+// (distance 32, 16, ... 1), the other lanes end with partial sums.  Kept apart because this launch is on the timed step and the xor
+// butterfly's lane arithmetic is eight instructions longer; no trailing barrier, so `red` serves one call.
+__device__ __forceinline__ float adam_lane0_total(float v, float* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(float* __restrict__ p, c
     }
   }
   if (gnorm_accum) {   // the gradient norm the trainer logs (clip_grad_norm_(inf), train.py:399), summed on the way
-    gsq = block_sum_256(gsq, red);
+    gsq = adam_lane0_total(gsq, red);
     if (threadIdx.x == 0) atomicAdd(gnorm_accum, gsq);
   }
 }

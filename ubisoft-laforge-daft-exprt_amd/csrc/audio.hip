@@ -32,7 +32,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_fir_kernel(const float* __restr
   const int b = blockIdx.y, tid = threadIdx.x;
   const long t0 = (long)blockIdx.x * RS_TILE;
   const long t1 = min(t0 + RS_TILE, S_out);
-  const long nb = min(max((long)n_in[b], 0L), S_in);
+  const long nb = dx_clamp_len(n_in, b, S_in);
   const long nf = nb * P / Q;
   if (blockIdx.x == 0 && tid == 0 && n_out) n_out[b] = (nb * P + Q - 1) / Q;
   float* yb = y + (long)b * ldy;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_copy_kernel(const float* __rest
                                                             long S_out) {
   const int b = blockIdx.y;
   const long t = (long)blockIdx.x * RS_THREADS + threadIdx.x;
-  const long nb = min(max((long)n_in[b], 0L), S_in);
+  const long nb = dx_clamp_len(n_in, b, S_in);
   if (t == 0 && n_out) n_out[b] = nb;
   if (t < S_out) y[(long)b * ldy + t] = t < nb ? x[(long)b * ldx + t] : 0.f;
 }
@@ -77,14 +77,9 @@ template <typename F>
 __device__ __forceinline__ long ft_prefix(int b, F v, long* red) {
   long s = 0;
   for (int i = threadIdx.x; i < b; i += 256) s += v(i);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
+  return dx_block_sum<4, false>(s, red);                            // (one call per kernel: red is not used again)
 }
 
-__device__ __forceinline__ long ft_mel_len(const int64_t* len, int i, int T) { return min(max((long)len[i], 0L), (long)T); }
 __device__ __forceinline__ long ft_wav_len(const int64_t* crop, int i) { return max((long)crop[2 * i + 1], 0L); }
 
 // grid (ceil(n_mel * T / 1024), B): mel_out[off_b + m * T_b + f] = mel[b, m, f], f < T_b = lengths[b]
@@ -92,8 +87,8 @@ __global__ __launch_bounds__(256) void ft_mel_kernel(const float* __restrict__ m
                                                      int n_mel, int T, float* __restrict__ out) {
   __shared__ long red[4];
   const int b = blockIdx.y;
-  const long Tb = ft_mel_len(len, b, T);
-  const long off = (long)n_mel * ft_prefix(b, [&](int i) { return ft_mel_len(len, i, T); }, red);
+  const long Tb = dx_clamp_len(len, b, T);
+  const long off = (long)n_mel * ft_prefix(b, [&](int i) { return dx_clamp_len(len, i, T); }, red);
   const long n = (long)n_mel * Tb;
   for (long e = (long)blockIdx.x * 1024 + threadIdx.x; e < min(n, (long)(blockIdx.x + 1) * 1024); e += 256) {
     const long m = e / Tb, f = e - m * Tb;

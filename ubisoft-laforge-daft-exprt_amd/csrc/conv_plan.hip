@@ -13,9 +13,7 @@ __device__ __forceinline__ void conv_plan_body(const int64_t* __restrict__ lens,
   auto tiles_at = [&](int H) {
     int c = 0;
     for (int b = lane; b < B; b += 64) c += (len_of(b) + H - 1) / H;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    return c;
+    return dx_wave_sum(c);
   };
   int lo = 1, hi = DX_PLAN_ROWS;                       // smallest height whose tile count fits (T >= B * ceil(N / 256) by contract)
   while (lo < hi) {
@@ -32,8 +30,7 @@ __device__ __forceinline__ void conv_plan_body(const int64_t* __restrict__ lens,
   // padding rows of the batch, split evenly over the T workgroups (entry.w)
   long dead = 0;
   for (int b = lane; b < B; b += 64) dead += N - len_of(b);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) dead += __shfl_xor(dead, o, 64);
+  dead = dx_wave_sum(dead);
   const int per = (int)((dead + T - 1) / T);
   for (int b = lane; b < B; b += 64) {
     const int l = len_of(b), t = first[b + 1] - first[b];

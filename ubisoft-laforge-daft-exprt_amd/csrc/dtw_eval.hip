@@ -26,8 +26,6 @@ __device__ __forceinline__ float dtw_dist(const float* __restrict__ r, const flo
   return sqrtf(acc);
 }
 
-__device__ __forceinline__ int dtw_len(const int64_t* n, int b, int T) { return (int)min(max((long)n[b], 0L), (long)T); }
-
 // ---- cepstrum: cep[b, t, k] = sum_m dct[k, m] * mel[b, m, t], t < n[b]; zeros behind ------------------------------------------
 __global__ __launch_bounds__(CEP_THREADS) void mel_cepstrum_kernel(const float* __restrict__ mel, long ld_b, long ld_m,
                                                                    const int64_t* __restrict__ n, const float* __restrict__ dct,
@@ -38,7 +36,7 @@ __global__ __launch_bounds__(CEP_THREADS) void mel_cepstrum_kernel(const float* 
   __syncthreads();
   if (t >= T) return;
   float* out = cep + ((long)b * T + t) * K;
-  if (t >= dtw_len(n, b, T)) {
+  if (t >= (int)dx_clamp_len(n, b, T)) {
     for (int k = 0; k < K; ++k) out[k] = 0.f;
     return;
   }
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_align_kernel(const float* __r
   __shared__ unsigned char s_code[DTW_MAX_LEN];                 // per reference frame: the code byte in progress
   __shared__ int s_len;
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int nr = dtw_len(n_ref, b, T_ref), nd = dtw_len(n_gen, b, T_gen);
+  const int nr = (int)dx_clamp_len(n_ref, b, T_ref), nd = (int)dx_clamp_len(n_gen, b, T_gen);
   const int P = T_ref + T_gen - 1;
   int* out = path + (long)b * P * 2;
   if (nr == 0 || nd == 0) {                                     // (uniform over the workgroup)
@@ -135,23 +133,6 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_align_kernel(const float* __r
 }
 
 // ---- scores along a path --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double dtw_wave_sum(double v) {       // xor butterfly: every lane ends with the same bits
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-// sum of v over the workgroup, every thread gets it; the order depends on the thread count alone
-__device__ __forceinline__ double dtw_block_sum(double v, double* red) {
-  v = dtw_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < DTW_WAVES; ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
-
 __global__ __launch_bounds__(DTW_THREADS) void dtw_path_scores_kernel(const float* __restrict__ cep_ref, const int64_t* __restrict__ n_ref,
                                                                       const float* __restrict__ cep_gen, const int64_t* __restrict__ n_gen,
                                                                       const int* __restrict__ path, const int* __restrict__ path_len,
@@ -162,7 +143,7 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_path_scores_kernel(const floa
                                                                       int* __restrict__ used_len, int T_ref, int T_gen, int K) {
   __shared__ double s_red[DTW_WAVES];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int nr = dtw_len(n_ref, b, T_ref), nd = dtw_len(n_gen, b, T_gen);
+  const int nr = (int)dx_clamp_len(n_ref, b, T_ref), nd = (int)dx_clamp_len(n_gen, b, T_gen);
   const int P = T_ref + T_gen - 1;
   const int len = min(max(path_len[b], 0), P);
   const int* pp = path + (long)b * P * 2;
@@ -187,8 +168,8 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_path_scores_kernel(const floa
       }
     }
   }
-  sd = dtw_block_sum(sd, s_red); cnt = dtw_block_sum(cnt, s_red);
-  sq = dtw_block_sum(sq, s_red); both = dtw_block_sum(both, s_red); one = dtw_block_sum(one, s_red);
+  sd = dx_block_sum<DTW_WAVES>(sd, s_red); cnt = dx_block_sum<DTW_WAVES>(cnt, s_red);
+  sq = dx_block_sum<DTW_WAVES>(sq, s_red); both = dx_block_sum<DTW_WAVES>(both, s_red); one = dx_block_sum<DTW_WAVES>(one, s_red);
   if (tid == 0) {
     const float nan = __builtin_nanf("");
     const double scale = 10.0 * 1.41421356237309504880 / 2.30258509299404568402;      // 10 sqrt(2) / ln 10

@@ -130,16 +130,67 @@ __device__ __forceinline__ float dx_row16_sum(float v) {
   return v;
 }
 
-__device__ __forceinline__ float dx_wave_sum(float v) {
+// ---- collective primitives: the ONE statement of every wave / workgroup reduction and scan outside the conv GEMM family and
+// attention.hip (DESIGN "Collective primitives").  A kernel calls these; it does not spell a butterfly of its own.
+// Sum over the wave (float, double, int, long, long long).  An xor butterfly, pairs at distance 32, 16, ... 1: every lane ends with
+// the same bits, and the association depends on the lane positions alone -- never on the batch around the row being summed.
+template <typename T>
+__device__ __forceinline__ T dx_wave_sum(T v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+// min / max over the wave, every lane gets it (exact whatever the order; NaN as fminf / fmaxf)
 __device__ __forceinline__ float dx_wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
+__device__ __forceinline__ float dx_wave_min(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+// Inclusive scan over the wave (int, long, long long, double): lane i returns x_0 + ... + x_i, added in the fixed order of the
+// doubling steps (exact for the integers).  `lane` is the caller's lane index (threadIdx.x itself in a single-wave kernel).
+template <typename T>
+__device__ __forceinline__ T dx_wave_scan(T x, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { const T y = __shfl_up(x, off, 64); if (lane >= off) x += y; }
+  return x;
+}
+// Sum of v over a workgroup of WAVES waves, every thread gets it: the wave butterfly, one slot of `red` (WAVES entries of LDS) per
+// wave, then red[0] + red[1] + ... from left to right -- the order depends on the wave count alone.  Every thread must call it.
+// The trailing barrier frees `red` for the next call; a caller that uses `red` once leaves it out (REUSE = false).
+template <int WAVES, bool REUSE = true, typename T>
+__device__ __forceinline__ T dx_block_sum(T v, T* red) {
+  v = dx_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T s = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) s += red[w];
+  if (REUSE) __syncthreads();
+  return s;
+}
+// One chunk (WAVES * 64 items, one per thread) of a workgroup exclusive scan with a running carry: returns carry + the items of
+// the threads below and adds the chunk's total to carry (the same in every thread).  s_part: WAVES entries of LDS.  Every thread
+// must call it, and a barrier must separate it from the next step, which rewrites s_part.
+template <int WAVES, typename T>
+__device__ __forceinline__ T dx_block_scan_step(T v, T& carry, T* s_part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const T x = dx_wave_scan(v, lane);
+  if (lane == 63) s_part[wave] = x;
+  __syncthreads();
+  T woff = carry, chunk = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) { const T t = s_part[w]; if (w < wave) woff += t; chunk += t; }
+  carry += chunk;
+  return woff + x - v;
+}
+// entry b of a lengths tensor as the kernels use it: never negative, never past what the buffers hold (cap: an int or a long)
+template <typename C>
+__device__ __forceinline__ long dx_clamp_len(const int64_t* n, int b, C cap) { return min(max((long)n[b], 0L), (long)cap); }
 
 // ---- per-utterance work lists without serial walks over the batch ------------------------------------------------------
 // Several kernels split a flat list of work items (64-row items, 128-row tiles) over their workgroups, where utterance b owns
@@ -150,6 +201,8 @@ __device__ __forceinline__ float dx_wave_max(float v) {
 // build the exclusive prefix sums in LDS, and the rest are LDS reads.
 //   s_val[b] = val_of(b), s_cum[b] = items before utterance b, s_cum[B] = total.   s_part: THREADS / 64 ints.
 // Every thread of the workgroup must call it (it has barriers); B <= DX_SCAN_MAXB (callers fall back to the serial walk above that).
+// The loop body is dx_block_scan_step written out: called through the helper, the weight-gradient kernels on the train step get
+// another register assignment, and their listings are kept as they are.
 constexpr int DX_SCAN_MAXB = 512;    // (LDS: two arrays of this many ints per workgroup; the largest published batch is 256 utterances)
 template <int THREADS, typename FV, typename FC>
 __device__ __forceinline__ void dx_block_count_scan(int B, FV val_of, FC cnt_of, int* s_val, int* s_cum, int* s_part) {
@@ -159,9 +212,7 @@ __device__ __forceinline__ void dx_block_count_scan(int B, FV val_of, FC cnt_of,
     const int b = b0 + tid;
     const int val = b < B ? val_of(b) : 0;
     const int v = b < B ? cnt_of(val) : 0;
-    int x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int y = __shfl_up(x, off, 64); if (lane >= off) x += y; }
+    const int x = dx_wave_scan(v, lane);
     if (lane == 63) s_part[wave] = x;
     __syncthreads();
     int woff = carry, chunk = 0;

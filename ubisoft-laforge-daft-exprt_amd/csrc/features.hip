@@ -17,17 +17,6 @@ __global__ __launch_bounds__(256) void wav_crop_kernel(const float* __restrict__
   }
 }
 
-__device__ __forceinline__ long wave_sum_long(long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_double(double v) {      // xor butterfly: every lane ends with the same bits
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // One wave per utterance.  The frame count of a row depends on that row's (begin, end) alone, so the rows are counted in
 // parallel (lane = row) and the reference's serial `while curr_frame <= nb_frames: pop(0)` becomes a prefix sum: row l is
 // popped iff the frames assigned before it are fewer than nb_frames.  Times in fp64, everything else in integers.
@@ -38,8 +27,7 @@ __global__ __launch_bounds__(64) void marker_durations_kernel(const double* __re
   const int b = blockIdx.x, lane = threadIdx.x;
   const double* sp = spans + (long)b * L * 2;
   int64_t* o = out + (long)b * L;
-  long rows = n_rows[b];
-  rows = rows < 0 ? 0 : (rows > L ? L : rows);
+  const long rows = dx_clamp_len(n_rows, b, L);
   const long n = n_samples[b];
   const long nb_frames = 1 + (long)((double)(n - fl) / (double)hop);     // int() truncates toward zero, like the cast
   const long half = (long)((double)fl / 2.0);
@@ -58,9 +46,7 @@ __global__ __launch_bounds__(64) void marker_durations_kernel(const double* __re
     const long l = l0 + lane;
     bool zero_len = false;
     const long c = l < rows ? count(l, &zero_len) : 0;
-    long x = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const long y = __shfl_up(x, off, 64); if (lane >= off) x += y; }
+    const long x = dx_wave_scan(c, lane);
     const bool pop = l < rows && assigned + x - c < nb_frames;
     if (__ballot(pop && zero_len)) st = 2;                               // ValueError: a popped row of zero length
     popped += __popcll(__ballot(pop));
@@ -89,7 +75,7 @@ __global__ __launch_bounds__(64) void marker_durations_kernel(const double* __re
     }
     o[l] = v;
   }
-  total = wave_sum_long(total);
+  total = dx_wave_sum(total);
   any_zero = __ballot(any_zero) != 0;
   if (!st) {
     const long mel_frames = centered ? 1 + n / hop : (n >= fl ? 1 + (n - fl) / hop : 0);
@@ -111,16 +97,13 @@ __global__ __launch_bounds__(64) void symbol_pool_kernel(const float* __restrict
   const float* e = energy + (long)b * ldt;
   const float* p = log_pitch + (long)b * ldt;
   const int64_t* d = durations + (long)b * L;
-  long rows = n_rows[b];
-  rows = rows < 0 ? 0 : (rows > L ? L : rows);
+  const long rows = dx_clamp_len(n_rows, b, L);
   long first = 0;                                                        // first frame of the chunk's first row
   for (long l0 = 0; l0 < L; l0 += 64) {
     const long l = l0 + lane;
     long dl = l < rows ? (long)d[l] : 0;
     if (dl < 0) dl = 0;
-    long x = dl;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const long y = __shfl_up(x, off, 64); if (lane >= off) x += y; }
+    const long x = dx_wave_scan(dl, lane);
     const long start = first + x - dl;
     first += __shfl(x, 63, 64);
     float out_e = 0.f, out_p = 0.f;
@@ -135,9 +118,9 @@ __global__ __launch_bounds__(64) void symbol_pool_kernel(const float* __restrict
         const float pv = p[f];
         if (pv > 0.f) { spv += (double)pv; ++voiced; }
       }
-      se = wave_sum_double(se);
-      spv = wave_sum_double(spv);
-      voiced = wave_sum_long(voiced);
+      se = dx_wave_sum(se);
+      spv = dx_wave_sum(spv);
+      voiced = dx_wave_sum(voiced);
       if (lane == r) {
         out_e = (float)(se / (double)dr);
         out_p = voiced ? (float)(spv / (double)voiced) : 0.f;

@@ -29,7 +29,6 @@ constexpr float PT_VOICING_COST = 0.4f;
 constexpr float PT_NO_STATE = 1e30f;
 constexpr float PT_LN2 = 0.69314718055994530942f;
 
-__device__ __forceinline__ long pt_clamp_n(const int64_t* n_samples, int b, long S) { return min(max((long)n_samples[b], 0L), S); }
 __device__ __forceinline__ int pt_n_analysis(long n, double step) { return 1 + (int)floor((double)n / step); }
 
 // grid B: mean_sq[b] = mean of x^2 over the utterance, in double, summed in a fixed order (thread-strided, then a tree)
@@ -37,7 +36,7 @@ __global__ __launch_bounds__(PT_THREADS) void pt_mean_sq_kernel(const float* __r
                                                                 long S, double* __restrict__ mean_sq) {
   __shared__ double red[PT_THREADS];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const long n = pt_clamp_n(n_samples, b, S);
+  const long n = dx_clamp_len(n_samples, b, S);
   const float* x = wav + (long)b * ldw;
   double s = 0.0;
   for (long i = tid; i < n; i += PT_THREADS) { const double v = x[i]; s += v * v; }
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(PT_THREADS) void pt_candidates_kernel(const float* 
   float* pl = pv + n_lags;                               // its interpolated lag
   __shared__ float out_lag[PT_K], out_val[PT_K];
   const int a = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const long n = pt_clamp_n(n_samples, b, S);
+  const long n = dx_clamp_len(n_samples, b, S);
   float* ol = cand_lag + ((long)b * A + a) * PT_K;
   float* ov = cand_val + ((long)b * A + a) * PT_K;
   if (a >= pt_n_analysis(n, step)) {
@@ -84,9 +83,7 @@ __global__ __launch_bounds__(PT_THREADS) void pt_candidates_kernel(const float* 
     const int chunk = (span + 63) / 64, i0 = min(tid * chunk, span), i1 = min(i0 + chunk, span);
     double s = 0.0;
     for (int i = i0; i < i1; ++i) { const double v = xs[i]; s += v * v; }
-    double incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const double y = __shfl_up(incl, off, 64); if (tid >= off) incl += y; }
+    const double incl = dx_wave_scan(s, tid);
     double run = incl - s;
     for (int i = i0; i < i1; ++i) { pre[i] = run; const double v = xs[i]; run += v * v; }
     if (tid == 63) pre[span] = incl;
@@ -137,7 +134,7 @@ __global__ __launch_bounds__(64) void pt_viterbi_kernel(const float* __restrict_
                                                         float* __restrict__ hz, float* __restrict__ log_pitch, int64_t* __restrict__ n_frames,
                                                         long S, int A, int T, int sr, double step, int hop, int lag_max, float uv_cost) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  const long n = pt_clamp_n(n_samples, b, S);
+  const long n = dx_clamp_len(n_samples, b, S);
   const int Ab = min(pt_n_analysis(n, step), A);
   const float* cl = cand_lag + (long)b * A * PT_K;
   const float* cv = cand_val + (long)b * A * PT_K;
@@ -174,10 +171,7 @@ __global__ __launch_bounds__(64) void pt_viterbi_kernel(const float* __restrict_
       c = local >= PT_NO_STATE ? PT_NO_STATE : best + local;
       if (state) bk[(long)a * (PT_K + 1) + lane] = (unsigned char)arg;
     }
-    float m = c;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fminf(m, __shfl_xor(m, off, 64));
-    cost = c - m;
+    cost = c - dx_wave_min(c);
     loglag = ll;
   }
   float best = 3e38f;

@@ -14,24 +14,6 @@ constexpr int PCC_MAX_LEN = 4096;      // longest curve (T_ref, T_dut); LDS: 2 c
 constexpr int PCC_THREADS = 256;
 constexpr int PCC_WAVES = PCC_THREADS / 64;
 
-__device__ __forceinline__ double pcc_wave_sum(double v) {       // xor butterfly: every lane ends with the same bits
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// sum of v over the workgroup, every thread gets it; the order depends on the thread count alone
-__device__ __forceinline__ double pcc_block_sum(double v, double* red) {
-  v = pcc_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < PCC_WAVES; ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
-
 // stable compaction of src[0, n) into dst (LDS): the elements > 0 in order when `drop`, all of them otherwise.  A ballot gives a
 // lane its place inside the wave, the wave totals of a 256-element chunk are combined through LDS.  Returns the kept length.
 __device__ __forceinline__ int pcc_compact(const float* __restrict__ src, int n, bool drop, float* dst, int* cnt) {
@@ -73,7 +55,7 @@ __global__ __launch_bounds__(PCC_THREADS) void curve_pcc_kernel(const float* __r
   __shared__ double s_red[PCC_WAVES];
   __shared__ int s_cnt[PCC_WAVES];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int nr = (int)min(max((long)n_ref[b], 0L), (long)T_ref), nd = (int)min(max((long)n_dut[b], 0L), (long)T_dut);
+  const int nr = (int)dx_clamp_len(n_ref, b, T_ref), nd = (int)dx_clamp_len(n_dut, b, T_dut);
 
   // 1. unvoiced removal
   const int num = pcc_compact(ref + (long)b * ld_ref, nr, drop != 0, s_ref, s_cnt);
@@ -89,7 +71,7 @@ __global__ __launch_bounds__(PCC_THREADS) void curve_pcc_kernel(const float* __r
   //    curve's variation only (a log-Hz curve is 5 +- 0.3)
   double acc = 0.0;
   for (int i = tid; i < Nx; i += PCC_THREADS) acc += (double)s_dut[i];
-  const float mean_x = (float)(pcc_block_sum(acc, s_red) / (double)Nx);
+  const float mean_x = (float)(dx_block_sum<PCC_WAVES>(acc, s_red) / (double)Nx);
   for (int i = tid; i < Nx; i += PCC_THREADS) s_dut[i] -= mean_x;
   pcc_table(s_tw, Nx);
   __syncthreads();
@@ -155,13 +137,13 @@ __global__ __launch_bounds__(PCC_THREADS) void curve_pcc_kernel(const float* __r
   // 5. Pearson in two passes: the means, then the centred sums
   double sr = 0.0, sy = 0.0;
   for (int i = tid; i < num; i += PCC_THREADS) { sr += (double)s_ref[i]; sy += (double)s_dut[i]; }
-  const double mr = pcc_block_sum(sr, s_red) / (double)num, my = pcc_block_sum(sy, s_red) / (double)num;
+  const double mr = dx_block_sum<PCC_WAVES>(sr, s_red) / (double)num, my = dx_block_sum<PCC_WAVES>(sy, s_red) / (double)num;
   double srr = 0.0, syy = 0.0, sry = 0.0;
   for (int i = tid; i < num; i += PCC_THREADS) {
     const double dr = (double)s_ref[i] - mr, dy = (double)s_dut[i] - my;
     srr = fma(dr, dr, srr); syy = fma(dy, dy, syy); sry = fma(dr, dy, sry);
   }
-  srr = pcc_block_sum(srr, s_red); syy = pcc_block_sum(syy, s_red); sry = pcc_block_sum(sry, s_red);
+  srr = dx_block_sum<PCC_WAVES>(srr, s_red); syy = dx_block_sum<PCC_WAVES>(syy, s_red); sry = dx_block_sum<PCC_WAVES>(sry, s_red);
   if (tid == 0) {
     const double sd_r = sqrt(srr / (double)num), sd_y = sqrt(syy / (double)num);
     pcc[b] = (sd_r > 0.0 && sd_y > 0.0) ? (float)((sry / (double)num) / (sd_y * sd_r)) : __builtin_nanf("");

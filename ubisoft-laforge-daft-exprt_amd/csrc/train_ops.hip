@@ -3,15 +3,6 @@
 
 namespace {
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  v = dx_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float t = red[0] + red[1] + red[2] + red[3];
-  __syncthreads();
-  return t;
-}
-
 // ------------------------------------------------------------------ losses (loss.py:54-99)
 // terms[0..6] = speaker, post_mult, duration, energy, pitch, mel_l1, mel_l2 (already weighted); terms[7] = total
 struct SeqLossArgs {
@@ -32,7 +23,7 @@ __global__ __launch_bounds__(256) void seq_loss_kernel(SeqLossArgs a) {
     acc += d * d;
     if (dp) dp[l] = a.gscale * a.w[f] * 2.f * d * inv;
   }
-  acc = block_sum_256(acc, red);
+  acc = dx_block_sum<4>(acc, red);
   if (threadIdx.x == 0) {
     if (a.part) a.part[f * a.B + b] = a.w[f] * acc * inv;
     else atomicAdd(a.terms + 2 + f, a.w[f] * acc * inv);
@@ -54,8 +45,8 @@ __global__ __launch_bounds__(256) void mel_loss_kernel(const float* __restrict__
     a2 += d * d;
     if (dpred) dpred[dtrans ? base + (i % T) * C + i / T : base + i] = gscale * w * ((d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) + 2.f * d) * inv;
   }
-  a1 = block_sum_256(a1, red);
-  a2 = block_sum_256(a2, red);
+  a1 = dx_block_sum<4>(a1, red);
+  a2 = dx_block_sum<4>(a2, red);
   if (threadIdx.x == 0) { atomicAdd(terms + 5, w * a1 * inv); atomicAdd(terms + 6, w * a2 * inv); }
 }
 
@@ -107,8 +98,8 @@ __global__ __launch_bounds__(256) void mel_loss_t_kernel(const float* __restrict
     }
     __syncthreads();
   }
-  a1 = block_sum_256(a1, red);
-  a2 = block_sum_256(a2, red);
+  a1 = dx_block_sum<4>(a1, red);
+  a2 = dx_block_sum<4>(a2, red);
   if (threadIdx.x == 0) {
     if (part) { part[2 * (b * gridDim.x + blockIdx.x)] = w * a1 * inv; part[2 * (b * gridDim.x + blockIdx.x) + 1] = w * a2 * inv; }
     else { atomicAdd(terms + 5, w * a1 * inv); atomicAdd(terms + 6, w * a2 * inv); }
@@ -140,10 +131,10 @@ __global__ __launch_bounds__(256) void head_loss_kernel(const float* __restrict_
       for (int s = 0; s < S; ++s)
         dlogits[(long)b * S + s] = gscale * w_spk * (expf(z[s] - mx) / se - (s == tgt ? 1.f : 0.f)) / (float)B;
   }
-  ce = block_sum_256(ce, red);
+  ce = dx_block_sum<4>(ce, red);
   float sq = 0.f;
   if (post) for (int i = threadIdx.x; i < npost; i += 256) sq += post[i] * post[i];
-  sq = block_sum_256(sq, red);
+  sq = dx_block_sum<4>(sq, red);
   const float nrm = sqrtf(sq);
   if (post && dpost) for (int i = threadIdx.x; i < npost; i += 256) dpost[i] += nrm > 0.f ? gscale * w_post * post[i] / nrm : 0.f;
   float t5[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -151,12 +142,12 @@ __global__ __launch_bounds__(256) void head_loss_kernel(const float* __restrict_
     for (int f = 0; f < 3; ++f) {
       float v = 0.f;
       for (int b = threadIdx.x; b < B; b += 256) v += seq_part[f * B + b];
-      t5[f] = block_sum_256(v, red);
+      t5[f] = dx_block_sum<4>(v, red);
     }
     float v1 = 0.f, v2 = 0.f;
     for (int i = threadIdx.x; i < n_mel_part; i += 256) { v1 += mel_part[2 * i]; v2 += mel_part[2 * i + 1]; }
-    t5[3] = block_sum_256(v1, red);
-    t5[4] = block_sum_256(v2, red);
+    t5[3] = dx_block_sum<4>(v1, red);
+    t5[4] = dx_block_sum<4>(v2, red);
   }
   if (threadIdx.x == 0) {
     terms[0] = w_spk * ce / (float)B;
@@ -201,7 +192,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
     for (long j = threadIdx.x; j < head; j += 256) a1 += x[j] * x[j];
     for (long j = head + nq * 4 + threadIdx.x; j < n; j += 256) a2 += x[j] * x[j];
   }
-  float acc = block_sum_256((a0 + a1) + (a2 + a3), red);
+  float acc = dx_block_sum<4>((a0 + a1) + (a2 + a3), red);
   if (threadIdx.x == 0) atomicAdd(out, acc);
 }
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -224,7 +215,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     p[i] = pi - step * mi / (sqrtf(vi) / bc2_sqrt + eps);
   }
   if (gnorm_accum) {   // the gradient norm the trainer logs (clip_grad_norm_(inf), train.py:399), summed on the way: no separate pass over g
-    gsq = block_sum_256(gsq, red);
+    gsq = dx_block_sum<4>(gsq, red);
     if (threadIdx.x == 0) atomicAdd(gnorm_accum, gsq);
   }
 }

@@ -65,12 +65,7 @@ __global__ __launch_bounds__(64) void gu_means_kernel(const int64_t* __restrict_
   for (int l0 = 0; l0 < L; l0 += 64) {
     const int l = l0 + lane;
     const long long d = l < L ? (long long)dur_int[(long)b * L + l] : 0;
-    long long incl = d;                       // inclusive wave scan, exact in int64
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
+    const long long incl = dx_wave_scan(d, lane);   // exact in int64
     const long long excl = carry + incl - d;
     if (l < L) {
       float mu = (float)d / 2.f;

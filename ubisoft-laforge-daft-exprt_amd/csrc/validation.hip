@@ -35,12 +35,7 @@ __global__ __launch_bounds__(VR_THREADS) void film_range_kernel(const float* __r
     const float x = film_value(film, i, blk, h, nb_blocks, width);
     if (isfinite(x)) { lo = fminf(lo, x); hi = fmaxf(hi, x); } else bad = 1;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, off, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    bad |= __shfl_xor(bad, off, 64);
-  }
+  lo = dx_wave_min(lo); hi = dx_wave_max(hi); bad = __ballot(bad) != 0;
   if ((tid & 63) == 0) { s_lo[tid >> 6] = lo; s_hi[tid >> 6] = hi; s_bad[tid >> 6] = bad; }
   __syncthreads();
   if (tid == 0) {
@@ -79,18 +74,6 @@ __global__ __launch_bounds__(VR_THREADS) void film_count_kernel(const float* __r
   if (tid < VR_BINS && s_cnt[tid]) atomicAdd(&counts[(long)g * VR_BINS + tid], (unsigned long long)s_cnt[tid]);
 }
 
-__device__ __forceinline__ double vr_block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < VR_WAVES; ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
-
 // one workgroup per utterance; dynamic LDS: (L + 1) ints, s_cum[l] = min(sum_{j < l} d_j, T_b) with d_j = 0 for j >= in_lengths[b]
 __global__ __launch_bounds__(VR_THREADS) void alignment_score_kernel(const float* __restrict__ weights, const int64_t* __restrict__ durations,
                                                                      const int64_t* __restrict__ in_lengths, const int64_t* __restrict__ out_lengths,
@@ -99,26 +82,17 @@ __global__ __launch_bounds__(VR_THREADS) void alignment_score_kernel(const float
   extern __shared__ int s_cum[];
   __shared__ long s_part[VR_WAVES];
   __shared__ double s_red[VR_WAVES];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Lb = (int)min(max((long)in_lengths[b], 0L), (long)L);
-  const long Tb = min(max((long)out_lengths[b], 0L), (long)T);
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Lb = (int)dx_clamp_len(in_lengths, b, L);
+  const long Tb = dx_clamp_len(out_lengths, b, T);
   const int64_t* d = durations + (long)b * L;
 
   // exact prefix sums, a chunk of VR_THREADS symbols at a time; every term is clamped to [0, Tb] first, so a long never overflows
   long carry = 0;
   for (int l0 = 0; l0 < L; l0 += VR_THREADS) {
     const int l = l0 + tid;
-    const long v = l < Lb ? min(max((long)d[l], 0L), Tb) : 0L;
-    long x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const long y = __shfl_up(x, off, 64); if (lane >= off) x += y; }
-    if (lane == 63) s_part[wave] = x;
-    __syncthreads();
-    long woff = carry, chunk = 0;
-#pragma unroll
-    for (int w = 0; w < VR_WAVES; ++w) { const long t = s_part[w]; if (w < wave) woff += t; chunk += t; }
-    if (l < L) s_cum[l] = (int)min(woff + x - v, Tb);
-    carry += chunk;
+    const long before = dx_block_scan_step<VR_WAVES>(l < Lb ? dx_clamp_len(d, l, Tb) : 0L, carry, s_part);
+    if (l < L) s_cum[l] = (int)min(before, Tb);
     __syncthreads();
   }
   if (tid == 0) s_cum[L] = (int)min(carry, Tb);
@@ -129,8 +103,7 @@ __global__ __launch_bounds__(VR_THREADS) void alignment_score_kernel(const float
   long hit = 0;
   double sum = 0.0;
   for (int t = tid; t < owned; t += VR_THREADS) {                // lanes walk along T: every load of the l loop is coalesced
-    int lo = 0, hi = Lb - 1;                                     // owner: the largest l with s_cum[l] <= t (symbols without frames are skipped)
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_cum[mid] <= t) lo = mid; else hi = mid - 1; }
+    const int lo = dx_locate_item(s_cum, Lb, t);                 // owner: the largest l with s_cum[l] <= t (symbols without frames are skipped)
     float best = w[t], at_owner = best;
     int arg = 0;
     for (int l = 1; l < Lb; ++l) {
@@ -141,7 +114,7 @@ __global__ __launch_bounds__(VR_THREADS) void alignment_score_kernel(const float
     hit += arg == lo;
     sum += (double)at_owner;
   }
-  const double tot = vr_block_sum(sum, s_red), nhit = vr_block_sum((double)hit, s_red);   // (counts below 2^31 are exact in a double)
+  const double tot = dx_block_sum<VR_WAVES>(sum, s_red), nhit = dx_block_sum<VR_WAVES>((double)hit, s_red);   // (counts below 2^31 are exact in a double)
   if (tid == 0) {
     frames[b] = owned;
     hits[b] = (int64_t)nhit;
