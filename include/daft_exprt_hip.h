@@ -745,6 +745,48 @@ int dx_dtw_path_scores(const float* cep_ref, const int64_t* n_ref, const float* 
                        float* f0_rmse_cents, float* vuv_error, int* voiced_pairs, int* used_len, int B, int T_ref, int T_gen,
                        int K, void* stream);
 
+/* ---- K26: batches collated on the device from a training set that is resident there.  Replaces DaftExprtDataCollate.__call__
+ * (data_loader.py:146-211: sort by phoneme count, right-zero-pad to the batch maxima) and the per-step H2D copy of its result.
+ * Additive entry points (the ABI version stays).
+ *
+ * The store, packed once by the caller (U utterances, utterance u with L_u symbols and T_u frames):
+ *   sym_off, frm_off (U + 1) int64: prefix sums of the L_u / T_u;   speaker (U) int64;
+ *   sym, dur_i (sum L) int32, dur_f, sym_en, sym_pi (sum L) fp32: symbol ids, durations_int, durations_float, symbols_energy,
+ *   symbols_pitch, utterance u at sym_off[u];
+ *   frm_en, frm_pi (sum T) fp32: frames_energy / frames_pitch, utterance u at frm_off[u];
+ *   mel (n_mel * sum T) fp32: utterance u at n_mel * frm_off[u], laid out as its .npy file is, (n_mel, T_u) row-major.
+ * Rows of the store are 4-byte aligned only; the kernels assume no more.  An index outside [0, U) is clamped into it.
+ *
+ * dx_collate_order (data_loader.py:158-166, 190-205): idx (n_micro * B) int64 = the utterances of n_micro micro-batches of B each, in
+ * the sampler's order (the same utterance may appear twice).  Each micro-batch is ordered on its own by L, descending and STABLE:
+ * entry b goes to row  #{j : L_j > L_b} + #{j < b : L_j == L_b}  of its micro-batch.  For every output row (n_micro * B, int64 each):
+ *   src_utt = the utterance, src_pos = its position b in the sampler's micro-batch, input_lengths = L, output_lengths = T,
+ *   speaker_ids;
+ * and, when the four bounds pointers are given (all or none), the `bounds` of a grouped step, with pads (n_micro, 2) int64 on the
+ * device = (L_pad, T_pad) of each micro-batch as the HOST computed them:
+ *   nmax_in / nmax_out = L_pad / T_pad of the row's own micro-batch,  skip_* = max(0, min(length, nmax - 2)).
+ * pads is never NULL (n_micro pairs; read only with bounds).  One workgroup per micro-batch, the B phoneme counts in LDS:
+ * B > dx_collate_max_batch() = 1024 returns DX_ERR_UNSUPPORTED before any launch.
+ *
+ * dx_collate_gather (data_loader.py:168-205): fills the padded batch of the rows src_utt (B_tot), in parse_batch's layout and dtypes:
+ *   o_sym, o_dur_i int64 (B_tot, L_pad);  o_dur_f, o_sym_en, o_sym_pi fp32 (B_tot, L_pad);
+ *   o_frm_en, o_frm_pi fp32 (B_tot, T_pad);  o_mel fp32 (B_tot, n_mel, T_pad).
+ * EVERY element of every output is written, padding as zero: the buffers need no memset.  L_pad / T_pad are the caller's (the
+ * allocation is); an utterance longer than them is cut.  A workgroup owns dx_collate_span() = 256 consecutive t (or l) of one row,
+ * one per lane, so reads and writes are both coalesced; a long row is split over ceil(T_pad / span) + ceil(L_pad / span) workgroups.
+ * B_tot > 65535: DX_ERR_UNSUPPORTED.  Neither entry point synchronises, allocates, or reads anything back. */
+long dx_collate_max_batch(void);
+long dx_collate_span(void);
+int dx_collate_order(const int64_t* idx, const int64_t* sym_off, const int64_t* frm_off, const int64_t* speaker, long U,
+                     const int64_t* pads, int64_t* src_utt, int64_t* src_pos, int64_t* input_lengths, int64_t* output_lengths,
+                     int64_t* speaker_ids, int64_t* skip_in, int64_t* nmax_in, int64_t* skip_out, int64_t* nmax_out, int n_micro,
+                     int B, void* stream);
+int dx_collate_gather(const int64_t* src_utt, const int64_t* sym_off, const int64_t* frm_off, long U, const int* sym,
+                      const float* dur_f, const int* dur_i, const float* sym_en, const float* sym_pi, const float* frm_en,
+                      const float* frm_pi, const float* mel, int64_t* o_sym, float* o_dur_f, int64_t* o_dur_i, float* o_sym_en,
+                      float* o_sym_pi, float* o_frm_en, float* o_frm_pi, float* o_mel, int B_tot, int L_pad, int T_pad, int n_mel,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

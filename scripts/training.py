@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """CLI of the training jobs, same flags as the reference `scripts/training.py:131-203` for the `train` and `fine_tune`
 sub-commands:
-    python scripts/training.py -en EXP -dd DATA_DIR -spks SPK [SPK ...] -lg english train [-chk CKPT] [-nmpd] [-ws N] [-r R] [-m URL]
+    python scripts/training.py -en EXP -dd DATA_DIR -spks SPK [SPK ...] -lg english train [-chk CKPT] [-nmpd] [-ws N] [-r R] [-m URL] [-rds]
     python scripts/training.py -en EXP -dd DATA_DIR -spks SPK [SPK ...] -lg english fine_tune -chk CKPT
 It builds `HyperParams`, writes `<experiment>/config.json` and runs `daft_exprt/train.py` or `daft_exprt/fine_tune.py` in a
 sub-process, like the reference (`training.py:101-128`).  `pre_process` is dataset tooling outside the accelerated path
@@ -48,7 +48,8 @@ def build_hparams(args, out_dir):
     features_dir = os.path.join(ROOT, 'datasets', args.language, '22050Hz')
     return HyperParams(training_files=os.path.join(features_dir, f'train_{args.language}.txt'),
                        validation_files=os.path.join(features_dir, f'validation_{args.language}.txt'), output_directory=out_dir,
-                       language=args.language, speakers=args.speakers, checkpoint=args.checkpoint)
+                       language=args.language, speakers=args.speakers, checkpoint=args.checkpoint,
+                       resident_data_set=bool(getattr(args, 'resident_data_set', False)))
 
 
 def parse_args(argv=None):
@@ -64,6 +65,8 @@ def parse_args(argv=None):
     p_train.add_argument('-ws', '--world_size', type=int, default=1)
     p_train.add_argument('-r', '--rank', type=int, default=0)
     p_train.add_argument('-m', '--master', type=str, default='tcp://localhost:54321')
+    # keep the training set in device memory and collate the batches there (daft_exprt/resident_set.py); not in the reference
+    p_train.add_argument('-rds', '--resident_data_set', action='store_true')
     p_fine_tune = sub.add_parser('fine_tune')
     p_fine_tune.add_argument('-chk', '--checkpoint', type=str, required=True)
     sub.add_parser('pre_process')

@@ -70,6 +70,9 @@ def _defaults():
         # the micro-batches of an optimizer step as ONE pass over their concatenation, each utterance keeping its own micro-batch's
         # padded length as a hard sequence end: same gradients as `accumulation_steps` separate passes (train.py:379-401)
         ('group_micro_batches', True),
+        # keep the training set in device memory and collate every batch there (`resident_set.py`); off by default.  A set whose
+        # packed size is above `resident_max_bytes` falls back to the DataLoader
+        ('resident_data_set', False), ('resident_max_bytes', 32 * 1024 ** 3),
         # must come from the caller
         ('training_files', None), ('validation_files', None), ('output_directory', None),
         ('language', None), ('speakers', None),

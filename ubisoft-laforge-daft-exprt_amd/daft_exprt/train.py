@@ -469,6 +469,14 @@ def _loaders(hparams, rank, world, distributed):
     ''' (train loader, validation loader or None): on-disk features when `training_files` exists, else the seeded synthetic
         utterances.  The sampler keys on the live process group (one predicate everywhere), not on the hparams flag. '''
     collate = DaftExprtDataCollate(hparams)
+    if getattr(hparams, 'resident_data_set', False) and os.path.isfile(str(hparams.training_files)):
+        # opt-in: the set lives in device memory and every batch is collated there (resident_set.py); the micro-batches of an
+        # optimizer step come out of the loader already grouped
+        from daft_exprt.resident_set import prepare_resident_loaders
+        group = hparams.accumulation_steps if getattr(hparams, 'group_micro_batches', True) else 1
+        train_loader, _, val_loader, _ = prepare_resident_loaders(hparams, torch.device('cuda', torch.cuda.current_device()),
+                                                                  distributed=distributed, group=group)
+        return train_loader, val_loader
     if os.path.isfile(str(hparams.training_files)):
         train_loader, _, val_loader, _ = prepare_data_loaders(hparams, num_workers=8, distributed=distributed)
         return train_loader, val_loader
@@ -559,13 +567,17 @@ def train(gpu, hparams, log_file):
 
     group = trainer.group and hparams.accumulation_steps > 1
 
+    resident = hasattr(loader, 'plan_epoch')      # a resident_set.ResidentLoader: its units are collated on the device
+    if resident:
+        loader.stream = copy_stream               # the collate launches run where the H2D copies of a host batch would
+
     held = []     # micro-batches of an unfinished group: carried over an epoch boundary like the reference's accumulation counter (train.py:391-397)
 
     def host_units():
         ''' collate outputs, one per forward / backward pass: the loader's batches, or -- grouped micro-batches -- the
             `accumulation_steps` batches of an optimizer step merged on the host (`group_host_batches`) '''
         for batch in loader:
-            if not group:
+            if not group or resident:            # (a resident loader yields the group itself and carries `held` on its own)
                 yield batch, None
                 continue
             held.append(batch)
@@ -582,10 +594,14 @@ def train(gpu, hparams, log_file):
             a copy stream under step i instead of in front of step i + 1 on the compute stream '''
         ahead = None
         for batch, grouped in host_units():
-            frames = int(batch[9].sum())     # host tensor (collate output): no device round trip
+            # host tensor (collate output): no device round trip; a resident unit carries the host's own count
+            frames = batch.frames if resident else int(batch[9].sum())
             with torch.cuda.stream(copy_stream):
-                inputs, targets, _ = model.parse_batch(gpu, batch)
-                unit = (inputs, targets)
+                if isinstance(batch, GroupedBatch):      # resident and grouped: complete as it is
+                    unit = batch
+                else:
+                    inputs, targets, _ = model.parse_batch(gpu, batch)      # (device tensors pass through)
+                    unit = (inputs, targets)
                 if grouped is not None:
                     (nmax_in, nmax_out), sizes = grouped
                     up = lambda t: t.to(inputs[5].device, non_blocking=True)
