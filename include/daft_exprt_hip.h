@@ -787,6 +787,40 @@ int dx_collate_gather(const int64_t* src_utt, const int64_t* sym_off, const int6
                       float* o_sym_pi, float* o_frm_en, float* o_frm_pi, float* o_mel, int B_tot, int L_pad, int T_pad, int n_mel,
                       void* stream);
 
+/* ---- K27: synthesis-based forced alignment -- from a recording and the model's own synthesis of the same text to the frames each
+ * symbol takes in the recording (daft_exprt/align.py; the reference starts from the .markers of an external aligner instead).
+ * Additive entry points (the ABI version stays).  Per row / pair, independently of the others: nothing at or past the row's own
+ * lengths is read, every output element is written, and the same bits come out alone, in any batch and with any padded extent.
+ *
+ * dx_active_span: energy (B, T) fp32, rows ld floats apart, with n_frames[b] <= T frames; rel_db <= 0 (DX_ERR_ARG otherwise).
+ *   peak = max(energy[b, :n]),  thr = peak * f in fp32, f = 10^(rel_db / 20) computed in double on the host and rounded once,
+ *   begin[b] = the first frame with energy >= thr,  end[b] = one past the last such frame           (int64 each).
+ * n == 0, or a peak that is not > 0, gives (0, 0).  One workgroup per row, workgroup reductions, no atomics.
+ *
+ * dx_dtw_transfer: path (B, T_ref + T_gen - 1, 2) int32 / path_len (B) int32 exactly as dx_dtw_align writes them, the i axis being
+ * the recording (n_ref[b] frames) and the j axis the synthesis (n_gen[b] frames); gen_durations (B, L) int64, the frames the model
+ * gave each symbol of its synthesis, n_symbols[b] <= L of them; min_frames >= 1 (DX_ERR_ARG otherwise).
+ *   A symbol s < n_symbols[b] with d_s > 0 is SOUNDING; its first synthesis frame is g_s = sum_{r < s} d_r.
+ *   raw start      a_s = min{ i : (i, g_s) is an entry of the path }       (entries that are no cell of the pair are skipped)
+ *   with the K sounding symbols in order, k = 0 .. K - 1:
+ *     forward      a_k = max(a_k, a_{k-1} + min_frames)                    k = 1 .. K - 1
+ *     then         a_k = min(a_k, n_ref - min_frames * (K - k))            k = 0 .. K - 1
+ *   rec_durations[b, s] = a_{k+1} - a_k, the last sounding symbol n_ref - a_k;  0 for silent symbols and for l >= n_symbols[b]
+ *   moved[b]  = how many starts the repair changed (int32): large where the synthesis and the recording disagree
+ *   status[b] = 0  ok: every sounding symbol has >= min_frames frames and the row sums to n_ref - a_0, which is n_ref for every
+ *                  path that starts in recording frame 0, as those of dx_dtw_align do
+ *               2  nothing to transfer: path_len 0, K == 0, a negative d_s, sum d != n_gen, or a g_s the path never visits
+ *               1  otherwise, n_ref < min_frames * K
+ *   (2 is decided before 1.)  With status != 0 all durations and moved are 0.
+ * Everything is integer.  One wave per pair: the per-frame minima in LDS (an integer minimum, whatever order the path entries
+ * arrive in), the symbols 64 at a time with wave scans, the repair serially over K <= n_gen values in LDS.
+ * T_ref, T_gen > dx_dtw_max_len() returns DX_ERR_UNSUPPORTED before any launch. */
+int dx_active_span(const float* energy, long ld, const int64_t* n_frames, float rel_db, int64_t* begin, int64_t* end, int B, int T,
+                   void* stream);
+int dx_dtw_transfer(const int* path, const int* path_len, const int64_t* n_ref, const int64_t* n_gen, const int64_t* gen_durations,
+                    const int64_t* n_symbols, int64_t* rec_durations, int* moved, int* status, int B, int T_ref, int T_gen, int L,
+                    int min_frames, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

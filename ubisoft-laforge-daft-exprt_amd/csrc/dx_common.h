@@ -173,6 +173,44 @@ __device__ __forceinline__ T dx_block_sum(T v, T* red) {
   if (REUSE) __syncthreads();
   return s;
 }
+// max / min of v over a workgroup of WAVES waves (float as fmaxf / fminf, or int), every thread gets it: the wave butterfly, one slot
+// of `red` per wave, then the slots from left to right.  Exact whatever the order.  Barriers and REUSE as in dx_block_sum.
+__device__ __forceinline__ int dx_wave_max(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+  return v;
+}
+__device__ __forceinline__ int dx_wave_min(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+  return v;
+}
+__device__ __forceinline__ float dx_max2(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ float dx_min2(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ int dx_max2(int a, int b) { return max(a, b); }
+__device__ __forceinline__ int dx_min2(int a, int b) { return min(a, b); }
+template <int WAVES, bool REUSE = true, typename T>
+__device__ __forceinline__ T dx_block_max(T v, T* red) {
+  v = dx_wave_max(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T s = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) s = dx_max2(s, red[w]);
+  if (REUSE) __syncthreads();
+  return s;
+}
+template <int WAVES, bool REUSE = true, typename T>
+__device__ __forceinline__ T dx_block_min(T v, T* red) {
+  v = dx_wave_min(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  T s = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) s = dx_min2(s, red[w]);
+  if (REUSE) __syncthreads();
+  return s;
+}
 // One chunk (WAVES * 64 items, one per thread) of a workgroup exclusive scan with a running carry: returns carry + the items of
 // the threads below and adds the chunk's total to carry (the same in every thread).  s_part: WAVES entries of LDS.  Every thread
 // must call it, and a barrier must separate it from the next step, which rewrites s_part.

@@ -323,6 +323,19 @@ def get_symbols_pitch(pitch, markers, device='cuda:0'):
     return _pool_one(pitch, markers, 1, device)
 
 
+def sentence_tokens(sentence):
+    ''' (tokens, closing) of a .lab sentence as `update_markers` reads it: lower-cased words and punctuation marks, the marks in
+        front of the first word dropped, those behind the last word taken off -- `closing` is the one right behind it, or None '''
+    kept = set(string.ascii_letters + punctuation)
+    tokens = [t for t in re.findall(rf"[\w']+|[{punctuation}]", sentence.lower().strip()) if kept.intersection(t)]
+    while tokens and tokens[0] in punctuation:
+        del tokens[0]
+    closing = None                               # of a run of closing marks the first one is kept
+    while tokens and tokens[-1] in punctuation:
+        closing = tokens.pop()
+    return tokens, closing
+
+
 def update_markers(file_name, lines, sentence, sent_begin, int_durations, hparams, logger):
     ''' `extract_features.py:114-219`: the aligner rows `begin end phone word word_idx` of one utterance become the rows
         `begin end int_dur symbol word word_idx` of its feature file: times counted from sent_begin, a word-boundary row (a
@@ -333,13 +346,7 @@ def update_markers(file_name, lines, sentence, sent_begin, int_durations, hparam
         this returns None as well.) '''
     if hparams.language != 'english':
         raise NotImplementedError()
-    kept = set(string.ascii_letters + punctuation)
-    tokens = [t for t in re.findall(rf"[\w']+|[{punctuation}]", sentence.lower().strip()) if kept.intersection(t)]
-    while tokens and tokens[0] in punctuation:
-        del tokens[0]
-    closing = None                               # of a run of closing marks the first one is kept
-    while tokens and tokens[-1] in punctuation:
-        closing = tokens.pop()
+    tokens, closing = sentence_tokens(sentence)
     rows = [line.strip().split(sep='\t') for line in lines]
     sentence_words = list(tokens)
 
