@@ -104,6 +104,20 @@ def test_captured_learning_rate_is_read_from_the_step_block(monkeypatch):
     assert 5. < float(d_big / d_small) < 20., (float(d_small), float(d_big))
 
 
+def test_prepare_keys_on_the_grouped_micro_batches(monkeypatch):
+    ''' accumulation with grouping on: `prepare` stores its graph under the key `step` looks up (both come through `Trainer.grouped`),
+        so the very next step over the same micro-batches replays it '''
+    hp, model, trainer, groups = _setup(monkeypatch, True, accum=2, n_batches=1)
+    cap = trainer.captured
+    assert trainer.group and len(groups[0]) == 2
+    assert cap.prepare(groups[0], 1)
+    assert cap.captures == 1 and cap.replays == 0 and cap.broken is None
+    trainer.step(groups[0], 2)
+    torch.cuda.synchronize()
+    assert cap.captures == 1 and cap.replays == 1 and cap.broken is None, (cap.captures, cap.replays, cap.broken)
+    assert torch.isfinite(model.flat_parameters()).all()
+
+
 def test_cache_policy(monkeypatch):
     hp, model, trainer, groups = _setup(monkeypatch, True, n_batches=4)
     cap = trainer.captured

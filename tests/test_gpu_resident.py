@@ -15,7 +15,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from daft_exprt import config
-from daft_exprt.data_loader import DaftExprtDataCollate, GroupedBatch, SyntheticUtterances, group_host_batches
+from daft_exprt.data_loader import DaftExprtDataCollate, GroupedBatch, HostUnits, SyntheticUtterances, finish_group, \
+    group_host_batches
 from daft_exprt.model import DaftExprt
 from daft_exprt.resident_set import GATHER_SPAN, ResidentBatch, ResidentLoader, ResidentSet, stable_order
 from tests.util import make_hparams
@@ -142,36 +143,74 @@ def test_more_rows_than_one_workgroups_lanes(poison):
     check_batch(hp, [store[i] for i in picks], loader.collate([picks]))
 
 
+GROUP_SHAPES = [(5, 9), (3, 14), (8, 21), (8, 6), (2, 31), (4, 17)]      # 3 x 2: (L_pad, T_pad) = (5, 14), (8, 21), (4, 31)
+# max(0, min(length, pad - 2)) of each of the six, worked out by hand
+GROUP_SKIP_IN, GROUP_SKIP_OUT = [3, 3, 6, 6, 2, 2], [9, 12, 19, 6, 29, 17]
+
+
+def group_rows(h_dirs, h_files, g):
+    ''' `match_rows` per micro-batch of 2: for every host row of the group, the device row of `g` with the same utterance '''
+    rows = []
+    for k in range(3):
+        sl = slice(2 * k, 2 * k + 2)
+        rows += [2 * k + r for r in match_rows(list(zip(h_dirs[sl], h_files[sl])), list(zip(g.dirs[sl], g.files[sl])))]
+    assert sorted(rows) == list(range(6))
+    return rows
+
+
+def assert_same_bounds(dev_bounds, host_bounds, rows):
+    assert len(dev_bounds) == len(host_bounds) == 4
+    for name, d, h in zip(('skip_in', 'nmax_in', 'skip_out', 'nmax_out'), dev_bounds, host_bounds):
+        assert d.dtype == h.dtype == torch.int64 and d.shape == h.shape and torch.equal(d[rows], h), name
+
+
 def test_grouped_micro_batches(poison):
     hp = make_hparams()
-    shapes = [(5, 9), (3, 14), (8, 21), (8, 6), (2, 31), (4, 17)]      # (L_pad, T_pad) = (5, 14), (8, 21), (4, 31)
+    shapes = GROUP_SHAPES
     store = [utterance(hp, k, L, T) for k, (L, T) in enumerate(shapes)]
     units = list(ResidentLoader(ResidentSet.from_items(store, hp, DEV), 2, shuffle=False, drop_last=True, group=3))
     assert len(units) == 1
     g = units[0]
     assert isinstance(g, GroupedBatch) and g.accum == 3 and g.sizes == [2, 2, 2]
     host = [DaftExprtDataCollate(hp)(store[2 * k:2 * k + 2]) for k in range(3)]
-    merged, (nmax_in, nmax_out), sizes = group_host_batches(host)
+    merged, nmax, sizes = group_host_batches(host)
     assert sizes == g.sizes and len(sizes) == g.accum
     inputs, targets, (h_dirs, h_files) = parse_host(hp, merged)
-    # the clamp as train() computes it
-    nmax_in, nmax_out = nmax_in.to(DEV), nmax_out.to(DEV)
-    bounds = (torch.clamp(torch.minimum(inputs[5], nmax_in - 2), min=0), nmax_in,
-              torch.clamp(torch.minimum(inputs[9], nmax_out - 2), min=0), nmax_out)
+    h = finish_group(inputs, targets, nmax, sizes)      # the host path's own finish of the group on the device
+    assert isinstance(h, GroupedBatch) and h.inputs is inputs and h.targets is targets and h.accum == 3 and h.sizes == sizes
+    skip_in, nmax_in, skip_out, nmax_out = h.bounds
     assert nmax_in.tolist() == [5, 5, 8, 8, 4, 4] and nmax_out.tolist() == [14, 14, 21, 21, 31, 31]
-    rows = []
-    for k in range(3):      # row matching is per micro-batch
-        sl = slice(2 * k, 2 * k + 2)
-        rows += [2 * k + r for r in match_rows(list(zip(h_dirs[sl], h_files[sl])), list(zip(g.dirs[sl], g.files[sl])))]
-    assert sorted(rows) == list(range(6))
+    rows = group_rows(h_dirs, h_files, g)
     assert_same_inputs(g.inputs, inputs, rows)
     assert g[0] is g.inputs and g[1] is g.targets and len(g.bounds) == 4
-    for name, d, h in zip(('skip_in', 'nmax_in', 'skip_out', 'nmax_out'), g.bounds, bounds):
-        assert d.dtype == h.dtype == torch.int64 and d.shape == h.shape and torch.equal(d[rows], h), name
+    assert_same_bounds(g.bounds, h.bounds, rows)
     for t, k in zip(g.targets, (1, 3, 4, 8, 10)):      # the views parse_batch hands out
         assert t is g.inputs[k]
     want = [int(p) for k in range(3) for p in stable_order([len(it[0]) for it in store[2 * k:2 * k + 2]])]
     assert g.order == want == g.device_order.tolist() and g.frames == sum(T for _, T in shapes)
+    # both paths against the hand-made values: device row r of micro-batch k holds utterance 2 k + order[r] of the store
+    utt = [2 * (r // 2) + p for r, p in enumerate(g.order)]
+    assert g.bounds[0].tolist() == [GROUP_SKIP_IN[u] for u in utt] and g.bounds[2].tolist() == [GROUP_SKIP_OUT[u] for u in utt]
+    assert skip_in.tolist() == [GROUP_SKIP_IN[utt[r]] for r in rows] and skip_out.tolist() == [GROUP_SKIP_OUT[utt[r]] for r in rows]
+
+
+def test_host_and_resident_feeders_yield_the_same_units(poison):
+    ''' `HostUnits` over a DataLoader and `ResidentLoader`, as the train loop drives them, over the same six utterances '''
+    hp = make_hparams()
+    store = [utterance(hp, k, L, T) for k, (L, T) in enumerate(GROUP_SHAPES)]
+    names = []
+    model = SimpleNamespace(parse_batch=lambda gpu, batch: (names.append((batch[11], batch[12])), parse_host(hp, batch))[1])
+    loader = torch.utils.data.DataLoader(store, batch_size=2, shuffle=False, drop_last=True, collate_fn=DaftExprtDataCollate(hp))
+    host_units = list(HostUnits(loader, 3).units(model, DEV))
+    resident = ResidentLoader(ResidentSet.from_items(store, hp, DEV), 2, shuffle=False, drop_last=True, group=3)
+    resident_units = list(resident.units(model, DEV))
+    assert len(host_units) == len(resident_units) == len(names) == 1 and resident.held == []
+    (h, h_frames), (g, g_frames) = host_units[0], resident_units[0]
+    assert isinstance(h, GroupedBatch) and isinstance(g, GroupedBatch) and h.accum == g.accum == 3 and h.sizes == g.sizes == [2, 2, 2]
+    rows = group_rows(*names[0], g)
+    assert_same_inputs(g.inputs, h.inputs, rows)
+    assert_same_bounds(g.bounds, h.bounds, rows)
+    assert h_frames == g_frames == sum(T for _, T in GROUP_SHAPES) and isinstance(h_frames, int) and isinstance(g_frames, int)
 
 
 def test_batches_do_not_depend_on_what_ran_before():

@@ -236,9 +236,7 @@ def group_micro_batches(micro_batches):
     ''' [(inputs 11-tuple, targets 5-tuple)] (host or device tensors, `parse_batch` order) -> GroupedBatch.  Plain torch copies:
         data staging like `parse_batch`, run once per optimizer step (or once per resident batch) outside the kernels' path. '''
     ins = [mb[0] for mb in micro_batches]
-    accum = len(ins)
-    Lg = max(i[0].shape[1] for i in ins)
-    Tg = max(i[8].shape[2] for i in ins)
+    Lg, Tg = max(i[0].shape[1] for i in ins), max(i[8].shape[2] for i in ins)
     cat = lambda idx, dim, size: torch.cat([_pad_to(i[idx], dim, size) for i in ins], 0).contiguous()
     inputs = (cat(0, 1, Lg), cat(1, 1, Lg), cat(2, 1, Lg), cat(3, 1, Lg), cat(4, 1, Lg), torch.cat([i[5] for i in ins]),
               cat(6, 1, Tg), cat(7, 1, Tg), cat(8, 2, Tg), torch.cat([i[9] for i in ins]), torch.cat([i[10] for i in ins]))
@@ -252,20 +250,78 @@ def group_micro_batches(micro_batches):
         assert all(t is not None for t in tg), 'group_micro_batches: targets given for some micro-batches only'
         tcat = lambda j, dim, size: torch.cat([_pad_to(t[j], dim, size) for t in tg], 0).contiguous()
         targets = (tcat(0, 1, Lg), tcat(1, 1, Lg), tcat(2, 1, Lg), tcat(3, 2, Tg), torch.cat([t[4] for t in tg]))
-    dev = inputs[5].device
-    nmax_in = torch.cat([torch.full((i[0].shape[0],), i[0].shape[1], dtype=torch.long, device=dev) for i in ins])
-    nmax_out = torch.cat([torch.full((i[8].shape[0],), i[8].shape[2], dtype=torch.long, device=dev) for i in ins])
-    skip_in = torch.clamp(torch.minimum(inputs[5], nmax_in - 2), min=0)
-    skip_out = torch.clamp(torch.minimum(inputs[9], nmax_out - 2), min=0)
-    return GroupedBatch(inputs, targets, (skip_in, nmax_in, skip_out, nmax_out), accum, [i[0].shape[0] for i in ins])
+    nmax = lambda k, dim: torch.cat([torch.full((i[k].shape[0],), i[k].shape[dim], dtype=torch.long, device=inputs[5].device) for i in ins])
+    return GroupedBatch(inputs, targets, group_bounds(inputs[5], nmax(0, 1), inputs[9], nmax(8, 2)), len(ins), [i[0].shape[0] for i in ins])
+
+
+def group_bounds(in_len, nmax_in, out_len, nmax_out):
+    ''' `GroupedBatch.bounds`: the one statement of the clamp skip = max(0, min(length, nmax - 2)) in Python (`dx_collate_order` has the device's) '''
+    skip = lambda length, nmax: torch.clamp(torch.minimum(length, nmax - 2), min=0)
+    return skip(in_len, nmax_in), nmax_in, skip(out_len, nmax_out), nmax_out
 
 
 def group_host_batches(batches):
-    ''' the same on collate outputs (13-tuples of host tensors): returns (13-tuple of the group, (nmax_in, nmax_out) host tensors, sizes);
-        `DaftExprt.parse_batch` and the clamp `skip = max(0, min(length, nmax - 2))` in `train()` finish the job on the device.
-        The caller checks `len(set(sizes)) == 1` (ragged micro-batches run one pass each, see `Trainer._grouped`) '''
-    ins = [(b[:11], None) for b in batches]
-    g = group_micro_batches(ins)
-    dirs = [d for b in batches for d in b[11]]
-    files = [f for b in batches for f in b[12]]
+    ''' `group_micro_batches` on collate outputs (13-tuples of host tensors): returns (13-tuple of the group, (nmax_in, nmax_out) host
+        tensors, sizes).  `DaftExprt.parse_batch` and `finish_group` make the `GroupedBatch` of it on the device (`HostUnits`). '''
+    g = group_micro_batches([(b[:11], None) for b in batches])
+    dirs, files = ([name for b in batches for name in b[k]] for k in (11, 12))
     return tuple(g.inputs) + (dirs, files), (g.bounds[1], g.bounds[3]), g.sizes
+
+
+def finish_group(inputs, targets, nmax, sizes):
+    ''' the `GroupedBatch` of `group_host_batches`' results, its 13-tuple gone through `parse_batch`; `nmax` goes up here, non-blocking '''
+    nmax_in, nmax_out = (t.to(inputs[5].device, non_blocking=True) for t in nmax)
+    return GroupedBatch(inputs, targets, group_bounds(inputs[5], nmax_in, inputs[9], nmax_out), len(sizes), sizes)
+
+
+def check_group_sizes(sizes):
+    ''' a ragged group would weigh an utterance 1 / B_total instead of the reference's 1 / (accum B_k) (the train loaders drop_last) '''
+    assert len(set(sizes)) == 1, f'micro-batches of different sizes {sizes}: set hparams.group_micro_batches = False'
+
+
+def take_groups(held, new, group):
+    ''' the carry-over rule: `held` + `new` in groups of `group` -> (groups, the incomplete rest: held for the next call, the next epoch's too) '''
+    items = list(held) + list(new)
+    n = len(items) // group
+    return [items[k * group:(k + 1) * group] for k in range(n)], items[n * group:]
+
+
+class HostUnits(object):
+    ''' a loader of collate outputs as a FEEDER of the train loop (`resident_set.ResidentLoader` is the other): an epoch of
+        `units(model, gpu)` yields (unit, valid frames) per forward / backward pass, unit = (inputs, targets) or -- group = accum > 1 --
+        the GroupedBatch of `accum` batches merged on the host before the H2D copy; its device work goes to `.stream` (None: current) '''
+    def __init__(self, loader, group=1):
+        self.loader, self.group, self.stream, self.held = loader, group, None, []
+
+    def plan(self):
+        ''' the host side of an epoch: (collate output, None) per batch, or (merged 13-tuple, (nmax, sizes)) per complete group '''
+        for batch in self.loader:
+            if self.group == 1:
+                yield batch, None
+                continue
+            groups, self.held = take_groups(self.held, [batch], self.group)
+            for members in groups:
+                merged, nmax, sizes = group_host_batches(members)
+                check_group_sizes(sizes)
+                yield merged, (nmax, sizes)
+
+    def units(self, model, gpu):
+        for batch, grouped in self.plan():
+            with torch.cuda.stream(self.stream):
+                unit = model.parse_batch(gpu, batch)[:2]
+                unit = unit if grouped is None else finish_group(*unit, *grouped)
+            yield unit, int(batch[9].sum())      # (a host tensor, the collate output: no device round trip)
+
+
+def prefetch(feeder, model, gpu):
+    ''' the feeder's units one ahead of the step that consumes them, as (unit, frames, ready): the H2D copies of unit i + 1 (15.8 MB
+        at B = 48) run on the feeder's stream under step i instead of in front of step i + 1 on the compute stream '''
+    ahead = None
+    for unit, frames in feeder.units(model, gpu):
+        ready = torch.cuda.Event()
+        ready.record(feeder.stream)
+        if ahead is not None:
+            yield ahead
+        ahead = (unit, frames, ready)
+    if ahead is not None:
+        yield ahead

@@ -5,7 +5,7 @@ standardisation with preserved zeros are therefore the loader's own bits), packs
 `ResidentLoader` stands in for the `DataLoader`: batch composition still comes from torch's sampler classes iterated on the host,
 but an epoch's index lists are uploaded once and every batch is two kernel launches (`dx_collate_order`, `dx_collate_gather`)
 that replace `DaftExprtDataCollate` (the reference's `data_loader.py:146-211`) and the per-step H2D copy.  Nothing during an epoch
-copies from the device or synchronises.  Opt-in (`hparams.resident_data_set`); the DataLoader path is untouched.
+copies from the device or synchronises.  Opt-in (`hparams.resident_data_set`); a feeder of the train loop like `data_loader.HostUnits`.
 """
 import logging
 import os
@@ -18,7 +18,7 @@ from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
 from torch.utils.data.distributed import DistributedSampler
 
 from daft_exprt import _hip as H
-from daft_exprt.data_loader import DaftExprtDataLoader, GroupedBatch, prepare_data_loaders
+from daft_exprt.data_loader import DaftExprtDataLoader, GroupedBatch, check_group_sizes, prepare_data_loaders, take_groups
 
 _logger = logging.getLogger(__name__)
 
@@ -170,15 +170,11 @@ class ResidentLoader(object):
         ''' one epoch's batches in the sampler's numbering (draws from torch's generator when shuffling) '''
         return [list(b) for b in self.batch_sampler]
 
-    def _local(self, batch):
-        return [self.set.local_of[int(g)] for g in batch] if self.distributed else batch
-
     def plan_epoch(self):
         ''' [[micro-batch (local indices), ...] per yield] of the next epoch; updates `held` '''
-        micro = self.held + [self._local(b) for b in self.index_lists()]
-        n = len(micro) // self.group
-        self.held = micro[n * self.group:] if self.group > 1 else []
-        return [micro[k * self.group:(k + 1) * self.group] for k in range(n)]
+        lists = [[self.set.local_of[int(g)] for g in b] if self.distributed else b for b in self.index_lists()]      # (a shard: local numbers)
+        plan, self.held = take_groups(self.held, lists, self.group)
+        return plan
 
     def __len__(self):
         ''' yields of the NEXT epoch (with a group, what is carried over counts) '''
@@ -186,6 +182,11 @@ class ResidentLoader(object):
 
     def __iter__(self):
         return self._run(self.plan_epoch())
+
+    def units(self, model, gpu):
+        ''' an epoch as the train loop's feeder (`data_loader.HostUnits`); `parse_batch` launches nothing: device tensors pass through '''
+        for batch in self:
+            yield (batch if self.group > 1 else model.parse_batch(gpu, batch)[:2]), batch.frames
 
     def collate(self, micro):
         ''' these micro-batches (lists of the set's own utterance numbers; `group` of them, one without a group) as one yield, now '''
@@ -198,8 +199,7 @@ class ResidentLoader(object):
             return
         for u in units:
             assert max(u.sizes) <= MAX_BATCH, f'batch of {max(u.sizes)} utterances: dx_collate_order takes at most {MAX_BATCH}'
-            # (like train(): a ragged group would weigh utterances 1 / B_total instead of the reference's 1 / (accum B_k))
-            assert len(set(u.sizes)) == 1, f'micro-batches of different sizes {u.sizes}: set hparams.group_micro_batches = False'
+            check_group_sizes(u.sizes)
         dev = self.set.device
         with torch.cuda.stream(self.stream):        # (None: the current stream)
             # the epoch's index lists and padded lengths: ONE upload

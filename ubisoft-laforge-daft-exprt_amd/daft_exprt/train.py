@@ -10,9 +10,8 @@ Step loop = `train.py:368-401, 475-494` with the device work restructured for MI
   * gradient all-reduce over RCCL/xGMI overlapped with backward, once per optimizer step (`parallel.GradReducer`);
   * fused Adam over the flat parameter buffer, bucket by bucket behind each bucket's all-reduce on an optimizer stream, the
     logged gradient norm summed on the way (`optim.FusedAdam`, `Trainer`);
-  * loss terms / gradient norm stay on the device; the scalars of iteration i reach the host (pinned copy on a side stream)
-    after iteration i + 1 has been enqueued, so logging every iteration like the reference (`train.py:404-423`; it does
-    8 `.item()` syncs per micro-batch, `loss.py:102-104`, `train.py:382`) costs no device idle time;
+  * loss terms / gradient norm stay on the device and reach the host one step behind (`StepLog`), so logging every iteration like the
+    reference (`train.py:404-423`; it does 8 `.item()` syncs per micro-batch, `loss.py:102-104`, `train.py:382`) costs no device idle time;
   * no per-iteration `dist.barrier()` (the reference's only paces log output, and its rank-local NaN test in front of it can
     deadlock): the gradient all-reduce keeps the ranks in step; validation and checkpoints keep their barriers.
 Validation scoring and the best-model checkpoint (`train.py:427-456`) are kept.  What the reference draws into TensorBoard at
@@ -32,8 +31,8 @@ import time
 import torch
 import torch.distributed as dist
 
-from daft_exprt.data_loader import DaftExprtDataCollate, GroupedBatch, SyntheticUtterances, group_host_batches, \
-    group_micro_batches, prepare_data_loaders
+from daft_exprt.data_loader import DaftExprtDataCollate, GroupedBatch, HostUnits, SyntheticUtterances, group_micro_batches, \
+    prefetch, prepare_data_loaders
 from daft_exprt.hparams import HyperParams
 from daft_exprt.loss import DaftExprtLoss, KEYS
 from daft_exprt.model import DaftExprt
@@ -119,10 +118,8 @@ class Trainer(object):
             self.reducer.broadcast_parameters()
         model.always_repack = False   # parameters only change through self.optimizer
         self.terms = None
-        # the `accumulation_steps` micro-batches of an optimizer step as ONE pass over their concatenation, every utterance keeping the
-        # padded length of its own micro-batch as a hard sequence end (`data_loader.GroupedBatch`): the reference's accumulation
-        # (`train.py:379-401`, default 16 x 3) at the launch count and tile efficiency of one batch of 48.  hparams.group_micro_batches
-        # = False keeps one pass per micro-batch.
+        # the `accumulation_steps` micro-batches of an optimizer step as ONE pass over their concatenation (`data_loader.GroupedBatch`,
+        # DESIGN 7a): the reference's 16 x 3 at the cost of one batch of 48.  hparams.group_micro_batches = False: one pass each.
         self.group = bool(getattr(hparams, 'group_micro_batches', True))
         self._groups = {}
         # per-bucket Adam behind each bucket's all-reduce: default on with several ranks (it hides the optimizer pass and the wait for
@@ -169,43 +166,39 @@ class Trainer(object):
             self.optimizer.step_slice(off, n)
         self._done.add(name)
 
-    def _grouped(self, micro_batches):
-        ''' the GroupedBatch of these micro-batches, or None when they cannot run as one pass (micro-batches of different sizes: the
-            group's per-utterance mean would weigh an utterance 1 / B_total instead of the reference's 1 / (accum B_k)).
+    def grouped(self, micro_batches):
+        ''' the list a step over these micro-batches runs, for `step`, `step_eager` and `CapturedStep.prepare` alike: their GroupedBatch alone,
+            or the list as it is -- a list of ONE (a group already), grouping off, host tensors, or ragged sizes (`check_group_sizes`).
             Resident batches are grouped once: the cache is keyed on the address AND the version counter of every source tensor (inputs
             and targets), so a caller that refills its staging buffers in place gets a fresh group '''
-        if len({mb[0][0].shape[0] for mb in micro_batches}) != 1:
-            return None
+        if not self.group or len(micro_batches) < 2 or not self.model.flat_parameters().is_cuda or \
+                len({mb[0][0].shape[0] for mb in micro_batches}) != 1:
+            return micro_batches
         srcs = [t for mb in micro_batches for part in mb for t in part]
         key = tuple((t.data_ptr(), t._version) for t in srcs)
         hit = self._groups.get(key)
         if hit is not None and all(x is y for x, y in zip(hit[0], srcs)):
-            return hit[1]
-        g = group_micro_batches(micro_batches)
+            return [hit[1]]
+        g = group_micro_batches(micro_batches)     # (outside a capture: the concatenation is input staging)
         if len(self._groups) >= 8:
             self._groups.pop(next(iter(self._groups)))
         self._groups[key] = (srcs, g)     # (keeps the source tensors alive: their addresses are part of the key)
-        return g
+        return [g]
 
     def step(self, micro_batches, iteration):
         ''' micro_batches: list of (inputs, targets) already on the device (len = accumulation_steps), or one
-            `data_loader.GroupedBatch` in a list (what `train()` builds on the host before the H2D copy).
+            `data_loader.GroupedBatch` in a list (what the train loop's feeders yield).
             Returns (terms (8,) device tensor summed over micro-batches / accumulation_steps, grad_norm_sq device scalar).
             The tensors may live in buffers a later call overwrites (captured steps reuse theirs): consume them -- or enqueue the
             copy that does -- before the next call. '''
-        if self.group and len(micro_batches) > 1 and self.model.flat_parameters().is_cuda:
-            g = self._grouped(micro_batches)                   # (outside a capture: the concatenation is input staging)
-            micro_batches = [g] if g is not None else micro_batches
         if self.captured is not None and not self.reducer.active and not self.sectioned:
-            return self.captured.step(micro_batches, iteration)
+            return self.captured.step(self.grouped(micro_batches), iteration)      # (keyed on the list that runs)
         return self.step_eager(micro_batches, iteration)
 
     def step_eager(self, micro_batches, iteration):
         ''' the step as individual launches (also what a capture records) '''
         hp, model = self.hp, self.model
-        if self.group and len(micro_batches) > 1 and model.flat_parameters().is_cuda:
-            g = self._grouped(micro_batches)
-            micro_batches = [g] if g is not None else micro_batches     # ragged micro-batches: one pass each, as the reference
+        micro_batches = self.grouped(micro_batches)
         accum = len(micro_batches)
         lr = update_learning_rate(hp, iteration)
         self.optimizer.param_groups[0]['lr'] = lr
@@ -341,6 +334,7 @@ class CapturedStep(object):
         ''' set-up call: make the graph of this step exist NOW (an eager step first, so that every kernel is loaded and the host-side
             caches are built -- a capture executes nothing -- then the capture), instead of on the second time `step` sees the key.
             Returns True when a graph for the key is cached afterwards. '''
+        micro_batches = self.tr.grouped(micro_batches)      # what `Trainer.step` will key on
         key = self.key(micro_batches)
         if key not in self.cache and self.broken is None and len(self.cache) < self.max_graphs:
             self.tr.step_eager(micro_batches, iteration)
@@ -465,21 +459,65 @@ def validate(gpu, model, criterion, val_loader, hparams, report=None):
     return val_loss / max(n, 1), {k: v / max(n, 1) for k, v in indiv.items()}
 
 
-def _loaders(hparams, rank, world, distributed):
-    ''' (train loader, validation loader or None): on-disk features when `training_files` exists, else the seeded synthetic
-        utterances.  The sampler keys on the live process group (one predicate everywhere), not on the hparams flag. '''
-    collate = DaftExprtDataCollate(hparams)
+def step_record(iteration, lr, duration, frames, values):
+    ''' an iteration's line of `metrics.jsonl` (names: DaftExprtLogger.log_training, logger.py:26-32); values = 7 `KEYS` terms, total, grad norm '''
+    return {'iteration': iteration, 'DaftExprt.optimization/grad_norm': values[8],
+            'DaftExprt.optimization/learning_rate': lr, 'DaftExprt.optimization/duration': duration,
+            'DaftExprt.training/loss': values[7], 'valid_frames': frames, **{f'DaftExprt.training/{k}': v for k, v in zip(KEYS, values[:7])}}
+
+
+class StepLog(object):
+    ''' per-iteration reporting (`train.py:404-423`) WITHOUT stalling the device: `push` behind step i copies its 9 scalars to pinned
+        memory on a side stream, `flush` reads them after step i + 1 has been enqueued -- the device always has the next step queued.
+        `start` = when the iteration being enqueued began, `total_time` = rank 0's logged durations since the last validation,
+        `pending` = (iteration, lr, valid frames) of the step whose scalars are in flight. '''
+    def __init__(self, gpu, rank, metrics_path):
+        self.rank, self.metrics_path, self.start, self.total_time, self.pending = rank, metrics_path, time.time(), 0., None
+        self.host = torch.empty(9, dtype=torch.float32).pin_memory()
+        self.stream = streams.pick([torch.cuda.current_stream(gpu)], what='log stream')      # (a hardware queue of its own: probed)
+        self.ready, self.step_done = torch.cuda.Event(), torch.cuda.Event()
+
+    def push(self, iteration, lr, frames, terms, gnorm_sq):
+        ''' behind the step just enqueued on the current stream: its scalars on their way to the host '''
+        stats_dev = torch.cat((terms, gnorm_sq.sqrt()))
+        self.step_done.record()
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(self.step_done)
+            self.host.copy_(stats_dev, non_blocking=True)
+            self.ready.record(self.stream)
+        stats_dev.record_stream(self.stream)
+        self.pending = (iteration, lr, frames)
+
+    def flush(self, now):
+        ''' log the pending iteration; returns False when its loss was NaN (the reference then logs nothing, train.py:404) '''
+        if self.pending is None:
+            return True
+        (iteration, lr, frames), self.pending = self.pending, None
+        self.ready.synchronize()             # waits for the END OF THE PREVIOUS step only
+        values = self.host.tolist()
+        duration, self.start = now - self.start, now      # host-enqueue interval of the iteration (the device runs one step behind the host)
+        if not math.isfinite(values[7]):
+            return False
+        if self.rank == 0:
+            self.total_time += duration
+            _logger.info(f'Train loss [{iteration}]: {values[7]:.6f} Grad Norm {values[8]:.6f} {duration:.2f}s/it (LR {lr:.6f})')
+            with open(self.metrics_path, 'a') as f:
+                f.write(json.dumps(step_record(iteration, lr, duration, frames, values)) + '\n')
+        return True
+
+
+def _loaders(hparams, rank, world, distributed, group):
+    ''' (feeder of the train loop, `group` micro-batches a unit; validation loader or None): on-disk features when `training_files` exists,
+        else the seeded synthetic utterances.  The sampler keys on the live process group (one predicate everywhere), not on the hparams flag. '''
     if getattr(hparams, 'resident_data_set', False) and os.path.isfile(str(hparams.training_files)):
-        # opt-in: the set lives in device memory and every batch is collated there (resident_set.py); the micro-batches of an
-        # optimizer step come out of the loader already grouped
-        from daft_exprt.resident_set import prepare_resident_loaders
-        group = hparams.accumulation_steps if getattr(hparams, 'group_micro_batches', True) else 1
-        train_loader, _, val_loader, _ = prepare_resident_loaders(hparams, torch.device('cuda', torch.cuda.current_device()),
-                                                                  distributed=distributed, group=group)
-        return train_loader, val_loader
+        # opt-in: the set lives in device memory and every batch is collated there (a set above `resident_max_bytes`: DataLoaders)
+        from daft_exprt import resident_set
+        train_loader, _, val_loader, _ = resident_set.prepare_resident_loaders(
+            hparams, torch.device('cuda', torch.cuda.current_device()), distributed=distributed, group=group)
+        return train_loader if isinstance(train_loader, resident_set.ResidentLoader) else HostUnits(train_loader, group), val_loader
     if os.path.isfile(str(hparams.training_files)):
         train_loader, _, val_loader, _ = prepare_data_loaders(hparams, num_workers=8, distributed=distributed)
-        return train_loader, val_loader
+        return HostUnits(train_loader, group), val_loader
     n_items = getattr(hparams, 'synthetic_items', hparams.batch_size * hparams.accumulation_steps * world * 8)
     ds = SyntheticUtterances(hparams, n_items, seed=hparams.seed, force_first_full=False)
     idx = list(range(rank, n_items, world))   # DistributedSampler(shuffle=False) striding (data_loader.py:232)
@@ -487,10 +525,11 @@ def _loaders(hparams, rank, world, distributed):
     # an utterance costs ~2 ms of numpy (100 ms per batch of 48): 16 processes feed an 8 ms step; with several ranks on one host the
     # ranks share its cores.  The workers come from a fork SERVER: forking a process that already holds HIP / RCCL threads is fragile
     workers = int(getattr(hparams, 'synthetic_workers', max(1, min(16, (os.cpu_count() or 16) // max(1, world)))))
-    return torch.utils.data.DataLoader(subset, batch_size=hparams.batch_size, shuffle=False, drop_last=True, collate_fn=collate,
-                                       num_workers=workers, pin_memory=True, persistent_workers=workers > 0,
-                                       prefetch_factor=4 if workers > 0 else None,
-                                       multiprocessing_context='forkserver' if workers > 0 else None), None
+    loader = torch.utils.data.DataLoader(subset, batch_size=hparams.batch_size, shuffle=False, drop_last=True, num_workers=workers,
+                                         collate_fn=DaftExprtDataCollate(hparams), pin_memory=True, persistent_workers=workers > 0,
+                                         prefetch_factor=4 if workers > 0 else None,
+                                         multiprocessing_context='forkserver' if workers > 0 else None)
+    return HostUnits(loader, group), None
 
 
 def train(gpu, hparams, log_file):
@@ -516,146 +555,51 @@ def train(gpu, hparams, log_file):
     model.train()
     trainer = Trainer(model, hparams, world)
     _logger.info(trainer.reducer.describe())   # rank 0: world size, backend and the bucket sizes (proof of the RCCL world in a log)
-    criterion = trainer.criterion
     iteration, best_val_loss = 1, float('inf')
     if hparams.checkpoint != '':
         model, trainer.optimizer, iteration, _, best_val_loss = load_checkpoint(hparams.checkpoint, gpu, model, trainer.optimizer, hparams)
         iteration += 1
-    loader, val_loader = _loaders(hparams, rank, world, distributed)
+    group = hparams.accumulation_steps if trainer.group else 1      # micro-batches in one unit of the feeder
+    feeder, val_loader = _loaders(hparams, rank, world, distributed, group)
     _logger.info(f'Batch size: {hparams.batch_size * hparams.accumulation_steps * world:_}')
     metrics_path = os.path.join(os.path.dirname(log_file), 'metrics.jsonl')
     ckpt_dir = os.path.join(hparams.output_directory, 'checkpoints')
-    start, total_time = time.time(), 0.
+    log = StepLog(gpu, rank, metrics_path)
     model.zero_grad()
     micro = []
-    # Per-iteration reporting (`train.py:404-423`) WITHOUT stalling the device: the 9 scalars of iteration i (7 loss terms, total,
-    # gradient norm) are copied to pinned memory on a side stream behind step i, and read by the host after step i + 1 has been
-    # enqueued -- the device always has the next step queued while the host formats the log line of the previous one.  The
-    # reference's per-iteration `dist.barrier()` (it only paces the ranks' log output) and the round-1 NaN all-reduce are gone:
-    # nothing in the step depends on them, and the gradient all-reduce already keeps the ranks in lockstep.
-    stats_host = torch.empty(9, dtype=torch.float32).pin_memory()
-    # (both helper streams on hardware queues other than the launch stream's: probed, `streams.pick`)
-    log_stream, stats_ready, step_done = streams.pick([torch.cuda.current_stream(gpu)], what='log stream'), torch.cuda.Event(), torch.cuda.Event()
-    pending = None        # (iteration, lr, valid frames) of the step whose scalars are in flight
-
-    def report(now):
-        ''' log the pending iteration; returns False when its loss was NaN (the reference then logs nothing, train.py:404) '''
-        nonlocal pending, total_time, start
-        if pending is None:
-            return True
-        it_p, lr_p, frames_p = pending
-        pending = None
-        stats_ready.synchronize()            # waits for the END OF THE PREVIOUS step only
-        values = stats_host.tolist()
-        tot_loss, grad_norm = values[7], values[8]
-        duration = now - start               # host-enqueue interval of the iteration (the device runs one step behind the host)
-        start = now
-        if not math.isfinite(tot_loss):
-            return False
-        if rank == 0:
-            total_time += duration
-            _logger.info(f'Train loss [{it_p}]: {tot_loss:.6f} Grad Norm {grad_norm:.6f} {duration:.2f}s/it (LR {lr_p:.6f})')
-            with open(metrics_path, 'a') as f:   # scalar names of DaftExprtLogger.log_training (logger.py:26-32)
-                rec = {'iteration': it_p, 'DaftExprt.optimization/grad_norm': grad_norm,
-                       'DaftExprt.optimization/learning_rate': lr_p, 'DaftExprt.optimization/duration': duration,
-                       'DaftExprt.training/loss': tot_loss, 'valid_frames': frames_p}
-                rec.update({f'DaftExprt.training/{k}': v for k, v in zip(KEYS, values[:7])})
-                f.write(json.dumps(rec) + '\n')
-        return True
-
-    copy_stream = streams.pick([torch.cuda.current_stream(gpu)], what='copy stream')
-
-    group = trainer.group and hparams.accumulation_steps > 1
-
-    resident = hasattr(loader, 'plan_epoch')      # a resident_set.ResidentLoader: its units are collated on the device
-    if resident:
-        loader.stream = copy_stream               # the collate launches run where the H2D copies of a host batch would
-
-    held = []     # micro-batches of an unfinished group: carried over an epoch boundary like the reference's accumulation counter (train.py:391-397)
-
-    def host_units():
-        ''' collate outputs, one per forward / backward pass: the loader's batches, or -- grouped micro-batches -- the
-            `accumulation_steps` batches of an optimizer step merged on the host (`group_host_batches`) '''
-        for batch in loader:
-            if not group or resident:            # (a resident loader yields the group itself and carries `held` on its own)
-                yield batch, None
-                continue
-            held.append(batch)
-            if len(held) == hparams.accumulation_steps:
-                merged, nmax, sizes = group_host_batches(held)
-                # (the train loader drops its last partial batch, data_loader.py:238; a ragged group would weigh utterances 1 / B_total
-                # instead of the reference's 1 / (accum B_k) -- ADVICE r5)
-                assert len(set(sizes)) == 1, f'micro-batches of different sizes {sizes}: set hparams.group_micro_batches = False'
-                held.clear()
-                yield merged, (nmax, sizes)
-
-    def device_batches():
-        ''' the loader's batches one ahead of the step that consumes them: the H2D copies of batch i + 1 (15.8 MB at B = 48) run on
-            a copy stream under step i instead of in front of step i + 1 on the compute stream '''
-        ahead = None
-        for batch, grouped in host_units():
-            # host tensor (collate output): no device round trip; a resident unit carries the host's own count
-            frames = batch.frames if resident else int(batch[9].sum())
-            with torch.cuda.stream(copy_stream):
-                if isinstance(batch, GroupedBatch):      # resident and grouped: complete as it is
-                    unit = batch
-                else:
-                    inputs, targets, _ = model.parse_batch(gpu, batch)      # (device tensors pass through)
-                    unit = (inputs, targets)
-                if grouped is not None:
-                    (nmax_in, nmax_out), sizes = grouped
-                    up = lambda t: t.to(inputs[5].device, non_blocking=True)
-                    nmax_in, nmax_out = up(nmax_in), up(nmax_out)
-                    bounds = (torch.clamp(torch.minimum(inputs[5], nmax_in - 2), min=0), nmax_in,
-                              torch.clamp(torch.minimum(inputs[9], nmax_out - 2), min=0), nmax_out)
-                    unit = GroupedBatch(inputs, targets, bounds, len(sizes), sizes)
-                ready = torch.cuda.Event()
-                ready.record(copy_stream)
-            if ahead is not None:
-                yield ahead
-            ahead = (unit, frames, ready)
-        if ahead is not None:
-            yield ahead
-
+    feeder.stream = streams.pick([torch.cuda.current_stream(gpu)], what='copy stream')      # H2D copies / collate launches, one unit ahead
     while iteration <= hparams.nb_iterations:
-        for unit, frames, ready in device_batches():
+        for unit, frames, ready in prefetch(feeder, model, gpu):
             main = torch.cuda.current_stream()
             main.wait_event(ready)
             for t in tuple(unit[0]) + (tuple(unit.bounds) if isinstance(unit, GroupedBatch) else ()):
                 t.record_stream(main)        # allocated on the copy stream, consumed on the compute stream
             micro.append((unit, frames))
-            if len(micro) < (1 if group else hparams.accumulation_steps):
+            if len(micro) < hparams.accumulation_steps // group:
                 continue
             terms, gnorm_sq = trainer.step([u for u, _ in micro], iteration)
             frames = sum(f for _, f in micro)
             micro = []
             lr = trainer.optimizer.param_groups[0]['lr']
-            report(time.time())              # the PREVIOUS iteration's scalars (this one is already queued on the device)
-            stats_dev = torch.cat((terms, gnorm_sq.sqrt()))
-            step_done.record()
-            with torch.cuda.stream(log_stream):
-                log_stream.wait_event(step_done)
-                stats_host.copy_(stats_dev, non_blocking=True)
-                stats_ready.record(log_stream)
-            stats_dev.record_stream(log_stream)
-            pending = (iteration, lr, frames)
+            log.flush(time.time())           # the PREVIOUS iteration's scalars (this one is already queued on the device)
+            log.push(iteration, lr, frames, terms, gnorm_sq)
             periodic = (val_loader is not None and iteration % hparams.iters_check_for_model_improvement == 0) or \
                 iteration % hparams.iters_per_checkpoint == 0 or iteration >= hparams.nb_iterations
             if periodic:
                 torch.cuda.synchronize()
-                report(time.time())          # validation / checkpoint / end of training: catch up first
+                log.flush(time.time())       # validation / checkpoint / end of training: catch up first
             # ---- model evaluation (`train.py:427-456`): every rank scores the whole validation set, rank 0 keeps the best
             if val_loader is not None and iteration % hparams.iters_check_for_model_improvement == 0:
                 _logger.info('Validating....')
                 vreport = ValidationReport(hparams, iteration, len(val_loader)) \
                     if rank == 0 and getattr(hparams, 'validation_report', True) else None
-                val_loss, val_indiv = validate(gpu, model, criterion, val_loader, hparams, report=vreport)
+                val_loss, val_indiv = validate(gpu, model, trainer.criterion, val_loader, hparams, report=vreport)
                 if rank == 0:
                     _logger.info(f'Validation loss {iteration}: {val_loss:.6f} ')
-                    remaining = int((hparams.nb_iterations - iteration) * (total_time / hparams.iters_check_for_model_improvement))
+                    remaining = int((hparams.nb_iterations - iteration) * (log.total_time / hparams.iters_check_for_model_improvement))
                     _logger.info(f'estimated required time = {remaining // 86400:02}:{remaining // 3600 % 24:02}:'
                                  f'{remaining // 60 % 60:02}:{remaining % 60:02}')
-                    total_time = 0.
+                    log.total_time = 0.
                     with open(metrics_path, 'a') as f:   # scalar names of DaftExprtLogger.log_validation (logger.py:41-45)
                         rec = {'iteration': iteration, 'DaftExprt.validation/loss': val_loss}
                         rec.update({f'DaftExprt.validation/{k}': v for k, v in val_indiv.items()})
@@ -684,7 +628,7 @@ def train(gpu, hparams, log_file):
                 generate_benchmark_sentences(model, hparams, os.path.join(ckpt_dir, f'chk_{iteration}'), iteration)
             iteration += 1
             if periodic:
-                start = time.time()          # validation / checkpoint time is not an iteration's duration (train.py:486)
+                log.start = time.time()      # validation / checkpoint time is not an iteration's duration (train.py:486)
             if iteration > hparams.nb_iterations:
                 break
     if distributed:
