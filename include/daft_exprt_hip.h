@@ -821,6 +821,79 @@ int dx_dtw_transfer(const int* path, const int* path_len, const int64_t* n_ref, 
                     const int64_t* n_symbols, int64_t* rec_durations, int* moved, int* status, int B, int T_ref, int T_gen, int L,
                     int min_frames, void* stream);
 
+/* ---- K28: a learned aligner -- soft alignment between frame queries and symbol keys, the forward-sum (monotonic, blank-free CTC)
+ * loss over it, and monotonic alignment search (MAS) for the hard path (daft_exprt/aligner.py; RAD-TTS / "One TTS Alignment to Rule
+ * Them All", Glow-TTS; the reference starts from the .markers of an external aligner instead).  Additive entry points (the ABI
+ * version stays).
+ *
+ * Common to the five entry points.  Utterance b has n_frm[b] <= T frames and n_sym[b] <= L symbols (int64, clamped into [0, T] /
+ * [0, L]); every tensor is contiguous in the shape given.  Utterances are independent of each other; nothing at or past n_frm[b] /
+ * n_sym[b] is read; EVERY output element is written (dead cells 0, -1 for the path); an utterance gives the same bits alone, in
+ * any batch, with any padded extent T / L and whatever the outputs and workspaces held before.  No atomics: two runs are bit-equal.
+ * T > dx_dtw_max_len() = 4096, L > dx_aln_max_symbols() = 1024 (one thread per symbol, one workgroup per utterance) or
+ * A > dx_aln_max_dim() = 256 returns DX_ERR_UNSUPPORTED before any launch, as does B > 65535.  All arithmetic is fp32.
+ * status[b] (forward sum and MAS): 2 when n_sym[b] == 0 or n_frm[b] == 0; otherwise 1 when n_frm[b] < n_sym[b] (no monotone path
+ * with one frame per symbol exists); otherwise 0.
+ *
+ * dx_aln_logprob_fwd: q (B, T, A), k (B, L, A), temperature > 0 (DX_ERR_ARG otherwise) -> logp (B, T, L).  For t < n_frm, l < n_sym:
+ *   d(t, l)     = sum_a (q[t, a] - k[l, a])^2          the difference form; a = 0 .. A - 1 in order, each term one fused multiply-add
+ *   prior(t, l) = -u^2 * c,  u = (l + 1/2) / n_sym - (t + 1/2) / n_frm,  c = 1 / (2 prior_sigma^2) computed in double on the host
+ *                 and rounded once;  0 when prior_sigma <= 0
+ *   s(t, l)     = fma(-temperature, d, prior)
+ *   logp(t, l)  = s(t, l) - (m + log(sum_l' exp(s(t, l') - m))),  m = max_l' s(t, l')
+ * One wave per frame; lane i holds the symbols l = i, i + 64, ...: it sums its exp terms in order of l, then the 64 lane sums go
+ * through the xor butterfly of dx_wave_sum (pairs at distance 32, 16, ... 1).  The order depends on l alone.
+ *
+ * dx_aln_logprob_bwd: q, k, logp as above and g = dLoss/dlogp (B, T, L) -> dq (B, T, A), dk (B, L, A); dead rows 0.
+ *   G(t)     = sum_l g(t, l)                           per lane in order of l = i, i + 64, ..., then the butterfly
+ *   ds(t, l) = g(t, l) - exp(logp(t, l)) * G(t)
+ *   dq[t, a] = -2 temperature * sum_l ds(t, l) (q[t, a] - k[l, a])        l = 0 .. n_sym - 1 in order, fused multiply-adds
+ *   dk[l, a] = +2 temperature * sum_t ds(t, l) (q[t, a] - k[l, a])        t = 0 .. n_frm - 1 in order, fused multiply-adds
+ * Two launches: one wave per frame (dq and G), then one workgroup per tile of 8 keys, one thread per (key, channel), which walks
+ * the frames itself: the sum over t is one thread's, hence deterministic.  row_ws: B * T floats of scratch (G).
+ *
+ * dx_aln_forward_sum: logp (B, T, L) -> alpha (B, T, L), loss (B), status (B) int32.
+ *   alpha(0, 0) = logp(0, 0),  alpha(0, l > 0) = -inf
+ *   alpha(t, l) = logp(t, l) + logaddexp(alpha(t - 1, l), alpha(t - 1, l - 1)),   alpha(t - 1, -1) = -inf
+ *   logaddexp(x, y) = max + log1p(exp(min - max));  -inf for two -inf, never NaN
+ *   loss[b] = -alpha(n_frm - 1, n_sym - 1)
+ * Live cells of alpha that no path from (0, 0) reaches hold -inf.  status != 0: loss NaN, alpha all 0.
+ *
+ * dx_aln_forward_sum_bwd: logp, alpha as dx_aln_forward_sum wrote it, w (B) = dLoss/dloss[b] -> dlogp (B, T, L).
+ *   beta(n_frm - 1, n_sym - 1) = 0, -inf for the other symbols of the last frame
+ *   beta(t, l)  = logaddexp(logp(t + 1, l) + beta(t + 1, l), logp(t + 1, l + 1) + beta(t + 1, l + 1)),   the second -inf at l + 1 = n_sym
+ *   gamma(t, l) = exp(alpha(t, l) + beta(t, l) - alpha(n_frm - 1, n_sym - 1))
+ *   dlogp(t, l) = -w[b] * gamma(t, l),  and exactly +0 where gamma is 0 (every cell no path visits)
+ * status != 0 (recomputed from the lengths): the row is all 0.
+ *
+ * dx_aln_mas: logp -> score (B) fp32, path (B, T + L - 1, 2) int32, path_len (B) int32, status (B) int32.
+ *   V(0, 0) = logp(0, 0),  V(0, l > 0) = -inf,  V(t, l) = logp(t, l) + max(V(t - 1, l), V(t - 1, l - 1))
+ * The predecessor of (t, l) is (t - 1, l); it is (t - 1, l - 1) only when that one is STRICTLY greater (the first-minimum rule of
+ * dx_dtw_align, mirrored).  score[b] = V(n_frm - 1, n_sym - 1).  path / path_len are laid out exactly as dx_dtw_align writes them for
+ * T_ref = T, T_gen = L, so dx_dtw_transfer reads them directly: the cells (t, l) from (0, 0) to (n_frm - 1, n_sym - 1), one entry per
+ * frame (path_len = n_frm), entries at or past path_len -1.  status != 0: path_len 0, score NaN, the path all -1.
+ * ws: ws_stride bytes of scratch per utterance, 8-byte aligned, ws_stride a multiple of 8 and >= 8 * T * ceil(L / 64) (DX_ERR_SHAPE
+ * otherwise): one direction bit per cell, frame t of utterance b in the 64-bit words ws[b][t * ceil(n_sym[b] / 64) ...], bit l & 63
+ * of word l >> 6.  Nothing in it has to be initialised or to survive the call, and its content is not trusted: the backtrack takes
+ * exactly n_frm - 1 moves and is forced at l = 0 (stay) and at t = l (step), so no workspace content can walk it out of the lattice.
+ *
+ * The three lattice kernels: one workgroup per utterance, thread l owns symbol l and keeps its value of the previous frame in a
+ * register; the l - 1 (l + 1) neighbour comes by one DPP move inside a wave, through a double-buffered LDS slot and one barrier per
+ * frame between waves; L <= 64 launches a one-wave kernel without barriers.  Rows are fetched 8 frames ahead. */
+long dx_aln_max_symbols(void);
+long dx_aln_max_dim(void);
+int dx_aln_logprob_fwd(const float* q, const float* k, const int64_t* n_frm, const int64_t* n_sym, float temperature,
+                       float prior_sigma, float* logp, int B, int T, int L, int A, void* stream);
+int dx_aln_logprob_bwd(const float* q, const float* k, const float* logp, const float* g, const int64_t* n_frm,
+                       const int64_t* n_sym, float temperature, float* dq, float* dk, float* row_ws, int B, int T, int L, int A,
+                       void* stream);
+int dx_aln_forward_sum(const float* logp, const int64_t* n_frm, const int64_t* n_sym, float* alpha, float* loss, int* status, int B,
+                       int T, int L, void* stream);
+int dx_aln_forward_sum_bwd(const float* logp, const float* alpha, const float* w, const int64_t* n_frm, const int64_t* n_sym,
+                           float* dlogp, int B, int T, int L, void* stream);
+int dx_aln_mas(const float* logp, const int64_t* n_frm, const int64_t* n_sym, float* score, int* path, int* path_len, int* status,
+               void* ws, long ws_stride, int B, int T, int L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -226,6 +226,19 @@ __device__ __forceinline__ T dx_block_scan_step(T v, T& carry, T* s_part) {
   carry += chunk;
   return woff + x - v;
 }
+// The value of the lane below / above in the wave (DPP wave_shr:1 / wave_shl:1: one VALU move, no trip through the LDS crossbar);
+// lane 0 / lane 63 gets `fill`.  Every lane of the wave must be active.
+__device__ __forceinline__ float dx_wave_shr1(float v, float fill) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float dx_wave_shl1(float v, float fill) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
+}
+// log(exp(a) + exp(b)) in fp32: max + log1p(exp(min - max)); two -inf give -inf, never NaN
+__device__ __forceinline__ float dx_logaddexp(float a, float b) {
+  const float m = fmaxf(a, b), n = fminf(a, b);
+  return m == -__builtin_inff() ? m : m + log1pf(expf(n - m));
+}
 // entry b of a lengths tensor as the kernels use it: never negative, never past what the buffers hold (cap: an int or a long)
 template <typename C>
 __device__ __forceinline__ long dx_clamp_len(const int64_t* n, int b, C cap) { return min(max((long)n[b], 0L), (long)cap); }

@@ -322,7 +322,10 @@ def _summary(records):
 
 def align_data_set(dataset_dir, speakers, phonemised_files, model, hparams, batch_size=32, min_frames=3, trim_db=-40.0,
                    overwrite=False, report_file=None, device='cuda:0'):
-    ''' for every speaker -- `<dataset_dir>/<speaker>/wavs/NAME.wav`, `<dataset_dir>/<speaker>/align/NAME.lab` and the `NAME|...`
+    ''' model: a `DaftExprt` (its synthesis is warped onto the recording, `align_batch`) or an `aligner.Aligner` (its learned
+        alignment, `Aligner.align_batch`: any speaker name goes, `frames_gen` is then the symbol count and `path_cost` the negative
+        MAS score per frame).
+        for every speaker -- `<dataset_dir>/<speaker>/wavs/NAME.wav`, `<dataset_dir>/<speaker>/align/NAME.lab` and the `NAME|...`
         lines of the speaker's phonemised file (`generate.read_phonemised_sentences`; phonemised_files: {speaker: path}, a list
         in the order of `speakers`, or one path for all) -- writes `<dataset_dir>/<speaker>/align/NAME.markers` from
         `align_batch`, batch_size utterances at a time: the wavs go to the device through `audio.device_waves`, the results come
@@ -333,11 +336,14 @@ def align_data_set(dataset_dir, speakers, phonemised_files, model, hparams, batc
         {status, moved, path_cost, frames, frames_gen, symbols, written}}, 'summary': {...}, 'skipped': [[speaker, NAME, reason]],
         'already_done', 'batches', 'seconds', 'min_frames', 'trim_db'}. '''
     from daft_exprt import audio
+    from daft_exprt.aligner import Aligner
     from daft_exprt.generate import _symbol_ids, read_phonemised_sentences
     from daft_exprt.write_behind import WriteBehind
     dev = H.device(device)
     fs = int(hparams.sampling_rate)
     speakers = list(speakers)
+    learned = isinstance(model, Aligner)     # a learned aligner (DESIGN 9l) knows no speakers: any name goes, the id is unused
+    run = model.align_batch if learned else (lambda *a: align_batch(model, *a))
     if isinstance(phonemised_files, (str, os.PathLike)):
         phonemised_files = {speaker: phonemised_files for speaker in speakers}
     elif not isinstance(phonemised_files, dict):
@@ -348,9 +354,9 @@ def align_data_set(dataset_dir, speakers, phonemised_files, model, hparams, batc
               'min_frames': int(min_frames), 'trim_db': float(trim_db)}
     start = time.time()
     for speaker in speakers:
-        if speaker not in hparams.speakers:
+        if not learned and speaker not in hparams.speakers:
             raise ValueError(f'speaker "{speaker}" is not one of the model\'s: {hparams.speakers}')
-        speaker_id = int(hparams.speakers_id[hparams.speakers.index(speaker)])
+        speaker_id = 0 if learned else int(hparams.speakers_id[hparams.speakers.index(speaker)])
         wavs_dir, align_dir = os.path.join(dataset_dir, speaker, 'wavs'), os.path.join(dataset_dir, speaker, 'align')
         for path in (wavs_dir, align_dir):
             if not os.path.isdir(path):
@@ -390,8 +396,7 @@ def align_data_set(dataset_dir, speakers, phonemised_files, model, hparams, batc
                 for b, u in enumerate(utts):
                     symbols[b, :len(u.ids)] = torch.tensor(u.ids, dtype=torch.int64)
                 ints = torch.tensor([[len(u.ids), speaker_id] for u in utts], dtype=torch.int64).to(dev)
-                out = align_batch(model, symbols.to(dev), ints[:, 0].contiguous(), wavs, n_total, ints[:, 1].contiguous(), hparams,
-                                  min_frames, trim_db)
+                out = run(symbols.to(dev), ints[:, 0].contiguous(), wavs, n_total, ints[:, 1].contiguous(), hparams, min_frames, trim_db)
                 named = [(key, out[key]) for key in ALIGN_KEYS]
                 layout = [(key, str(t.dtype).replace('torch.', ''), tuple(t.shape)) for key, t in named]
                 writer.put(torch.cat([t.contiguous().view(-1).view(torch.uint8) for _, t in named]), layout, utts)
