@@ -894,6 +894,55 @@ int dx_aln_forward_sum_bwd(const float* logp, const float* alpha, const float* w
 int dx_aln_mas(const float* logp, const int64_t* n_frm, const int64_t* n_sym, float* score, int* path, int* path_len, int* status,
                void* ws, long ws_stride, int B, int T, int L, void* stream);
 
+/* ---- K29: per-symbol prosody targets -- a recording's timing, loudness and intonation, symbol by symbol, imposed on the prosody
+ * predictor's outputs at synthesis time (daft_exprt/clone.py; the reference only scales the predictions by factors).  Additive entry
+ * points (the ABI version stays).  Per utterance, independently of the others: one wave each, fp64 sums in an order fixed by the row
+ * alone, no atomics, and the same bits alone, in any batch and with any padded extent.
+ *
+ * dx_clone_pool: energy / log_pitch (B, ldt) fp32 frame curves of the WHOLE recording with T <= ldt frames (pitch in natural-log Hz,
+ * 0 = unvoiced, as K20 / K17 give them), begin (B) int64 = the first frame of the sounding stretch, durations (B, L) int64 and n_rows
+ * (B) int64 as dx_symbol_pool takes them.  Row l < n_rows[b] with duration d > 0 owns the next d frames, the first row starting at
+ * begin[b]; pooling is dx_symbol_pool's: the mean of the row's frames, for pitch over the frames > 0 only and 0 when there is none,
+ * 0 for a row of duration 0, the sum in fp64, one rounding to fp32.  raw_energy / raw_pitch (B, L), each may be NULL: these means.
+ *   self_stats (B, 4) fp32 = (mean, std) of the utterance's own non-zero pooled energies, then of its non-zero pooled pitches: the
+ *     mean and the POPULATION std (as features_stats) of the fp32 means, two passes in fp64, rounded once; (0, 0) without a value.
+ *   sym_energy / sym_pitch (B, L): v != 0 ? (v - mean) / std : 0 in fp32 (data_loader._standardise: zeros stay exactly 0), with
+ *     mean_e / std_e and mean_p / std_p (B) fp32 when the pair is given, with the row's self_stats when the pair is NULL (a mean
+ *     without its std is DX_ERR_ARG).
+ *   dropped (B) int32: bit 0 (energy) / bit 1 (pitch) is set, and that quantity's outputs are all 0, when its statistics cannot
+ *     be used: self statistics of fewer than two non-zero values or with a std that is not > 0; a given std that is not > 0.
+ *   status (B) int32: 0, or 1 when begin[b] < 0, a duration is negative or begin[b] + sum of the durations > T: nothing is read
+ *     for such a row and all its outputs are 0.  Frames at or past T are never read.
+ * Every element of every output is written, rows l >= n_rows[b] as 0.
+ *
+ * dx_prosody_impose: in place on the predictor's dur (seconds), energy, pitch (B, L) fp32, for l < lengths[b] (the rest of a row is
+ * left alone).  t_dur_frames (B, L) int64 or NULL, an entry < 0 meaning "no target for this symbol"; t_energy / t_pitch (B, L) fp32
+ * or NULL; w_dur / w_energy / w_pitch (B, L) fp32 in [0, 1], each needed only with its target; dur_factors (B, L) fp32 or NULL (= 1).
+ *   x = w == 0 ? x : w == 1 ? t : fmaf(w, t - x, x)     w = 0 leaves x and w = 1 yields t, bit for bit
+ *   t_dur = frames * hop_length / sampling_rate, product and quotient in fp64, rounded once to fp32
+ *   a ZERO energy / pitch target is a statement (silent / unvoiced), not a number: x = 0 when w >= 0.5, x unchanged otherwise
+ *   exact[b] (B) int32 = 1 iff t_dur_frames is given and every l < lengths[b] has a target >= 0, w_dur == 1 and dur_factors == 1.0;
+ *     0 otherwise; -1 when a weight of the row that would be used is outside [0, 1] or NaN: such a row is left untouched.
+ * validate != 0: the weights are checked first and the call returns DX_ERR_ARG, naming the row, when one is outside [0, 1] -- this
+ * reads B ints back and synchronises the stream.  validate == 0 never synchronises; the bad row surfaces as status 4 below.
+ *
+ * dx_prosody_impose_durations runs after K16 (dx_int_durations), on its outputs: for a row with exact[b] == 1
+ *   durations_int[b, l] = t_dur_frames[b, l] for l < lengths[b] and 0 behind it,  totals[b] = their sum,
+ *   dur[b, l] = the target in seconds again for l < lengths[b] (K16 zeroes what is shorter than filter_length / sampling_rate / 2,
+ *   2 frames at the default settings; the integers of a recording hold symbols of 0, 1 and 2 frames, which K16 cannot return),
+ *   status[b] = 0, or 3 when the targets sum to 0 (the host raises: there is nothing to synthesise).
+ * A row with exact[b] == 0 keeps K16's result; one with exact[b] == -1 gets status 4 (the host raises). */
+int dx_clone_pool(const float* energy, const float* log_pitch, long ldt, const int64_t* begin, const int64_t* durations,
+                  const int64_t* n_rows, const float* mean_e, const float* std_e, const float* mean_p, const float* std_p,
+                  float* sym_energy, float* sym_pitch, float* raw_energy, float* raw_pitch, float* self_stats, int* dropped, int* status,
+                  int B, int T, int L, void* stream);
+int dx_prosody_impose(float* dur, float* energy, float* pitch, const int64_t* t_dur_frames, const float* t_energy, const float* t_pitch,
+                      const float* w_dur, const float* w_energy, const float* w_pitch, const int64_t* lengths, const float* dur_factors,
+                      int* exact, int B, int L, int hop_length, double sampling_rate, int validate, void* stream);
+int dx_prosody_impose_durations(const int* exact, const int64_t* t_dur_frames, const int64_t* lengths, float* dur,
+                                int64_t* durations_int, int64_t* totals, int* status, int B, int L, int hop_length, double sampling_rate,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,7 +100,7 @@ def _ref_name(ref, idx):
 
 def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_factors, batch_energy_factors, batch_pitch_factors,
                              pitch_transform, batch_speaker_ids, batch_file_names, output_dir, hparams, n_jobs=1,
-                             use_griffin_lim=True, scores=None, vocoder=None):
+                             use_griffin_lim=True, scores=None, vocoder=None, prosody_targets=None):
     ''' `generate.py:242-317`, same contract: every file name gets the `_spk_<id>_ref_<reference>` suffix IN PLACE
         (the caller's list is updated like the reference does, 248-253), one `model.inference` call on the collated
         batch, `<output_dir>/<file_name>.npz` holding `mel_spec` (298), and the return value
@@ -116,7 +116,10 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         `vocoder` (an extension): a `vocoder.Vocoder` (HiFi-GAN generator).  `<file_name>.wav` is then the vocoder's audio of the
         decoder's mel, made on the device before the copy to the host and written as 16-bit PCM (`audio.write_wav_int16`,
         `n_frames * hop` samples); `use_griffin_lim` is not needed and no preview is made; `scores` are computed on the vocoder's
-        audio.  With None nothing changes. '''
+        audio.  With None nothing changes.
+        `prosody_targets` (an extension): per sentence, in the caller's order, None or a one-row `clone.ProsodyTargets`
+        of that sentence's symbols: per-symbol durations (frames), energies and pitches imposed on the predictions; raw units are
+        standardised with the sentence's speaker.  The collate's sort is applied to them.  With None nothing changes. '''
     source = 'vocoder' if vocoder is not None else 'griffin_lim' if use_griffin_lim else None
     if scores is not None and source is None:
         raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
@@ -137,7 +140,17 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
             hparams.stats[f'spk {spk}']['pitch']             # KeyError like `model.py:824-825` when a speaker has no statistics
     inputs = tuple(t.to(gpu, non_blocking=True) for t in col[:-1])
     inference = model.inference if hasattr(model, 'inference') else model.module.inference   # DDP-wrapped callers (270-278)
-    encoder_preds, decoder_preds, alignments = inference(inputs, pitch_transform, hparams)
+    targets = None
+    if prosody_targets is not None:
+        from daft_exprt.clone import ProsodyTargets
+        assert len(prosody_targets) == len(batch_sentences), f'{len(prosody_targets)} prosody targets for {len(batch_sentences)} sentences'
+        targets = ProsodyTargets.stack(list(prosody_targets), int(col[4][0]), gpu)
+    if targets is None:
+        encoder_preds, decoder_preds, alignments = inference(inputs, pitch_transform, hparams)
+    else:       # the rows go where `collate_tensors` put their sentences: the same sort of the same symbol counts
+        order = torch.sort(torch.LongTensor([len(_symbol_ids(s, hparams)) for s in batch_sentences]), dim=0, descending=True)[1]
+        targets = targets.standardised(hparams, list(batch_speaker_ids)).permute(order)
+        encoder_preds, decoder_preds, alignments = inference(inputs, pitch_transform, hparams, prosody_targets=targets)
     if source == 'vocoder':              # HiFi-GAN audio, written as 16-bit PCM
         vocoder.check_hparams(hparams)
         wavs, n_samples = vocoder(decoder_preds[0].float().contiguous(), decoder_preds[1])
@@ -268,13 +281,13 @@ LAST_TIME_PERF = {}   # filled by generate_mel_specs(get_time_perf=True): what t
 
 def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_dir, hparams, dur_factors=None,
                        energy_factors=None, pitch_factors=None, batch_size=1, n_jobs=1, use_griffin_lim=False,
-                       get_time_perf=False, scores=None, vocoder=None):
+                       get_time_perf=False, scores=None, vocoder=None, prosody_targets=None):
     ''' `generate.py:320-437`, same contract: `pitch_factors = [transform, [per-sentence factor lists]]`, the list-length
         asserts, eval mode + no grad, chunks of `batch_size`, returns the predictions dict only.  With `get_time_perf`
         the real-time factor is logged exactly like the reference: wall time of the whole per-batch function (collate,
         H2D, inference, D2H, file writes) against `((n_frames - 1) * hop + n_fft - 2 * (n_fft // 2)) / sr` seconds of
-        audio per sentence (413-435); the numbers are also left in `LAST_TIME_PERF`.  `scores`, `vocoder`:
-        see `generate_batch_mel_specs`. '''
+        audio per sentence (413-435); the numbers are also left in `LAST_TIME_PERF`.  `scores`, `vocoder`,
+        `prosody_targets` (one entry per sentence, in the caller's order): see `generate_batch_mel_specs`. '''
     if scores is not None and not use_griffin_lim and vocoder is None:
         raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
     n = len(sentences)
@@ -287,17 +300,21 @@ def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_d
     for what, seq in (('filenames', file_names), ('speaker IDs', speaker_ids), ('references', refs),
                       ('duration factors', dur_factors), ('energy factors', energy_factors), ('pitch factors', pitch_factors)):
         assert len(seq) == n, _logger.error(f'{len(seq)} {what} but there are {n} sentences to generate')
+    if prosody_targets is not None:
+        assert len(prosody_targets) == n, _logger.error(f'{len(prosody_targets)} prosody targets but there are {n} sentences to generate')
     model.eval()
     os.makedirs(output_dir, exist_ok=True)
     predictions, time_per_batch = {}, []
     with torch.no_grad():
         for chunk in zip(chunker(sentences, batch_size), chunker(refs, batch_size), chunker(dur_factors, batch_size),
                          chunker(energy_factors, batch_size), chunker(pitch_factors, batch_size),
-                         chunker(speaker_ids, batch_size), chunker(file_names, batch_size)):
-            b_sent, b_refs, b_dur, b_en, b_pi, b_spk, b_names = chunk
+                         chunker(speaker_ids, batch_size), chunker(file_names, batch_size),
+                         chunker([None] * n if prosody_targets is None else list(prosody_targets), batch_size)):
+            b_sent, b_refs, b_dur, b_en, b_pi, b_spk, b_names, b_targets = chunk
             begin = time.time() if get_time_perf else None
+            extra = () if prosody_targets is None else (b_targets,)         # (without targets the call is the one it always was)
             predictions.update(generate_batch_mel_specs(model, b_sent, b_refs, b_dur, b_en, b_pi, pitch_transform, b_spk,
-                                                        b_names, output_dir, hparams, n_jobs, use_griffin_lim, scores, vocoder))
+                                                        b_names, output_dir, hparams, n_jobs, use_griffin_lim, scores, vocoder, *extra))
             time_per_batch += [time.time() - begin] if get_time_perf else []
     if get_time_perf:
         durations = []

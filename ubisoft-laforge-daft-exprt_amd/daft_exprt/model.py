@@ -1186,15 +1186,25 @@ class DaftExprt(nn.Module):
         return terms
 
     # ------------------------------------------------------------------ inference (`model.py:789-923`)
-    def get_int_durations(self, duration_preds, hparams, dur_factors=None):
+    def get_int_durations(self, duration_preds, hparams, dur_factors=None, frame_exact=None):
         ''' `model.py:789-812` on the device: thresholds `duration_preds` in place, returns (duration_preds, durations_int).
-            Raises IndexError like the reference when an utterance is shorter than one analysis window. '''
+            Raises IndexError like the reference when an utterance is shorter than one analysis window.
+            frame_exact (an extension): None, or (exact, targets, input_lengths) as `ops.prosody_impose` left them: the
+            rows with exact == 1 then get the targets' frames behind K16 (`dx_prosody_impose_durations`; those rows never raise K16's
+            IndexError), read back with the same one status copy. '''
         dint, totals, status = ops.int_durations(duration_preds, hparams, dur_factors)
+        if frame_exact is not None:
+            exact, targets, input_lengths = frame_exact
+            ops.prosody_impose_durations(exact, targets, input_lengths, duration_preds, dint, totals, status, hparams)
         st = status.cpu()
         if bool((st == 1).any()):
             raise IndexError('list index out of range')   # extract_features.py:90 / 104
         if bool((st == 2).any()):
             raise RuntimeError('shape mismatch: durations and non-zero symbols differ in number')   # model.py:808
+        if frame_exact is not None and bool((st == 3).any()):
+            raise ValueError(f'prosody targets: the duration targets of rows {torch.nonzero(st == 3).flatten().tolist()} sum to 0 frames')
+        if frame_exact is not None and bool((st == 4).any()):
+            raise ValueError(f'prosody targets: rows {torch.nonzero(st == 4).flatten().tolist()} have a weight outside [0, 1]')
         self._last_totals = totals
         return duration_preds, dint
 
@@ -1222,8 +1232,12 @@ class DaftExprt(nn.Module):
         return pitch_preds
 
     @torch.no_grad()
-    def inference(self, inputs, pitch_transform, hparams):
-        ''' `model.py:866-923` '''
+    def inference(self, inputs, pitch_transform, hparams, prosody_targets=None):
+        ''' `model.py:866-923`.  prosody_targets (an extension): None, or a `clone.ProsodyTargets` in standardised units
+            whose rows are the batch's: per-symbol durations (frames), energies and pitches imposed on the predictor's outputs before
+            the factors, the integer durations and the pitch transform.  `self.last_frame_exact` is then the (B,) int32 device
+            tensor of the rows whose integer durations ARE the targets, and None after a call without targets.  With None nothing
+            else is launched or allocated. '''
         symbols, dur_factors, energy_factors, pitch_factors, input_lengths, \
             energy_refs, pitch_refs, mel_spec_refs, ref_lengths, speaker_ids = inputs
         if pitch_transform not in ('add', 'multiply'):
@@ -1238,7 +1252,16 @@ class DaftExprt(nn.Module):
         enc, _ = self._phoneme_encoder_fwd(W, symbols, films[0], g_in, False, False)
         y, _ = self._predictor_fwd(W, enc, films[1], g_in, False, False)
         dur, energy, pitch = ops.unstack(y, 3)
-        dur, dur_int = self.get_int_durations(dur, hparams, dur_factors.contiguous())
+        self.last_frame_exact = None      # (of THIS call: never the flags of an earlier one)
+        if prosody_targets is None:
+            dur, dur_int = self.get_int_durations(dur, hparams, dur_factors.contiguous())
+        else:
+            if prosody_targets.units != 'standardised':
+                raise ValueError("inference takes prosody targets in standardised units: see ProsodyTargets.standardised")
+            dur_factors = dur_factors.contiguous()
+            exact = ops.prosody_impose(dur, energy, pitch, prosody_targets, input_lengths, dur_factors, hparams)
+            dur, dur_int = self.get_int_durations(dur, hparams, dur_factors, (exact, prosody_targets, input_lengths))
+            self.last_frame_exact = exact
         if pitch_transform == 'add':
             mean, std = self._speaker_stats(hparams, dur.device)
             ops.prosody_control(energy, pitch, energy_factors.contiguous(), pitch_factors.contiguous(), dur_int, 0, speaker_ids, mean, std)

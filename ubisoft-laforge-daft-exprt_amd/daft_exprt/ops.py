@@ -877,6 +877,63 @@ def prosody_control(energy, pitch, energy_factors, pitch_factors, durations_int,
                                        B, L, H.stream()))
 
 
+# ----------------------------------------------------------------------------- per-symbol prosody targets (K29)
+def clone_pool(energy, log_pitch, begin, durations, n_rows, energy_stats=None, pitch_stats=None, raw=False):
+    ''' `dx_clone_pool`: energy / log_pitch (B, T) fp32 frame curves of whole recordings, begin (B,) int64, durations (B, L) int64 and
+        n_rows (B,) int64 on the device; energy_stats / pitch_stats: None (the utterance's own statistics) or (mean, std) (B,) fp32.
+        Returns (sym_energy, sym_pitch (B, L) fp32 standardised, self_stats (B, 4) fp32, dropped (B,) int32, status (B,) int32), and
+        with `raw` the pooled means before standardisation (raw_energy, raw_pitch) behind them. '''
+    H.require_gpu(energy, log_pitch, begin, durations, n_rows)
+    assert energy.dtype == torch.float32 and log_pitch.dtype == torch.float32 and energy.dim() == 2 and energy.shape == log_pitch.shape
+    assert energy.stride(1) == 1 and log_pitch.stride(1) == 1 and energy.stride(0) == log_pitch.stride(0)
+    assert durations.dtype == torch.int64 and durations.dim() == 2 and durations.is_contiguous()
+    B, T = energy.shape
+    L = durations.shape[1]
+    assert durations.shape[0] == B and begin.dtype == torch.int64 and n_rows.dtype == torch.int64 and begin.shape == (B,) and n_rows.shape == (B,)
+    stats = []
+    for pair in (energy_stats, pitch_stats):
+        pair = (None, None) if pair is None else tuple(t.contiguous() for t in pair)
+        assert all(t is None or (t.dtype == torch.float32 and t.shape == (B,) and t.is_cuda) for t in pair)
+        stats += pair
+    dev = energy.device
+    outs = [_empty((B, L), dtype=torch.float32, device=dev) for _ in range(4 if raw else 2)]
+    self_stats = _empty((B, 4), dtype=torch.float32, device=dev)
+    dropped = _empty((B,), dtype=torch.int32, device=dev)
+    status = _empty((B,), dtype=torch.int32, device=dev)
+    H.check(H.lib().dx_clone_pool(H.ptr(energy), H.ptr(log_pitch), energy.stride(0), H.ptr(begin.contiguous()), H.ptr(durations),
+                                  H.ptr(n_rows.contiguous()), *[H.ptr(t) for t in stats], H.ptr(outs[0]), H.ptr(outs[1]),
+                                  H.ptr(outs[2]) if raw else None, H.ptr(outs[3]) if raw else None, H.ptr(self_stats), H.ptr(dropped),
+                                  H.ptr(status), B, T, L, H.stream()))
+    return (outs[0], outs[1], self_stats, dropped, status) + tuple(outs[2:])
+
+
+def prosody_impose(dur, energy, pitch, targets, lengths, dur_factors, hparams, validate=False):
+    ''' `dx_prosody_impose`, in place on the predictor's (B, L) fp32 outputs.  targets: an object with `durations` ((B, L) int64 frames,
+        < 0 where a symbol has none) / `energy` / `pitch` ((B, L) fp32, standardised), each a device tensor or None, and the (B, L) fp32
+        weights `w_dur` / `w_energy` / `w_pitch` of those given.  Returns exact (B,) int32.  `validate` reads the weight check back
+        (one synchronisation) and raises on a weight outside [0, 1]; without it such a row ends as status 4 of
+        `prosody_impose_durations`. '''
+    B, L = dur.shape
+    given = [getattr(targets, k) for k in ('durations', 'energy', 'pitch', 'w_dur', 'w_energy', 'w_pitch')]
+    for t, dtype in zip(given, (torch.int64,) + (torch.float32,) * 5):
+        assert t is None or (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (B, L) and t.is_contiguous()), \
+            f'prosody targets must be contiguous (B, L) = {(B, L)} device tensors'
+    assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (dur, energy, pitch)) and lengths.dtype == torch.int64
+    exact = _empty((B,), dtype=torch.int32, device=dur.device)
+    H.check(H.lib().dx_prosody_impose(H.ptr(dur), H.ptr(energy), H.ptr(pitch), *[H.ptr(t) for t in given], H.ptr(lengths),
+                                      H.ptr(dur_factors), H.ptr(exact), B, L, int(hparams.hop_length), float(hparams.sampling_rate),
+                                      int(bool(validate)), H.stream()))
+    return exact
+
+
+def prosody_impose_durations(exact, targets, lengths, dur, durations_int, totals, status, hparams):
+    ''' `dx_prosody_impose_durations`, in place on what `int_durations` returned: the rows with exact == 1 get the targets' frames '''
+    B, L = durations_int.shape
+    H.check(H.lib().dx_prosody_impose_durations(H.ptr(exact), H.ptr(targets.durations), H.ptr(lengths), H.ptr(dur), H.ptr(durations_int),
+                                                H.ptr(totals), H.ptr(status), B, L, int(hparams.hop_length),
+                                                float(hparams.sampling_rate), H.stream()))
+
+
 # ----------------------------------------------------------------------------- validation report
 FILM_BINS = 50
 
