@@ -943,6 +943,56 @@ int dx_prosody_impose_durations(const int* exact, const int64_t* t_dur_frames, c
                                 int64_t* durations_int, int64_t* totals, int* status, int B, int L, int hop_length, double sampling_rate,
                                 void* stream);
 
+/* ---- K30: a grapheme-to-phoneme model learned from a pronunciation dictionary -- the CTC loss of a word with its gradient, and greedy
+ * CTC decoding (daft_exprt/g2p.py; the reference runs `mfa g2p` on the words its dictionary lacks, generate.py:84-105).  Additive
+ * entry points (the ABI version stays).
+ *
+ * Common to both.  logits (B, T, V) fp32, contiguous; word b has n_steps[b] <= T output steps (int64, clamped into [0, T]); class 0
+ * is the blank.  Words are independent of each other; nothing at or past n_steps[b] / n_labels[b] is read; EVERY output element is
+ * written; a word gives the same bits alone, in any batch, with any padded extent T / U / B and whatever the outputs and the
+ * workspace held before.  No atomics: two runs are bit-equal.  T > dx_ctc_max_steps() = 256, U > dx_ctc_max_labels() = 127,
+ * V > dx_ctc_max_classes() = 128 or B > 262140 returns DX_ERR_UNSUPPORTED before any launch.  All arithmetic is fp32.
+ *   z(t)      = m + log(sum_v exp(x(t, v) - m)),  m = max_v x(t, v): lane i adds exp(x(t, i) - m) + exp(x(t, i + 64) - m) (a class at
+ *               or past V counts 0), then the 64 lane sums go through the xor butterfly of dx_wave_sum
+ *   lp(t, v)  = x(t, v) - z(t)
+ *
+ * dx_ctc_loss (generate.py:84-105): labels (B, U) int64 in [1, V - 1], n_labels[b] <= U of them (U = 0: labels may be NULL), w (B) fp32
+ * -> loss (B) fp32 = -log p(labels | logits), status (B) int32, grad (B, T, V) fp32 = w[b] * dloss[b] / dlogits, in ONE launch.
+ *   states s = 0 .. S - 1, S = 2 n_labels + 1: e(s) = blank for even s, labels[(s - 1) / 2] for odd s
+ *   skip(s) = s odd, s >= 3 and e(s) != e(s - 2)
+ *   lse3(a, b, c) = m + log(exp(a - m) + exp(b - m) + exp(c - m)), m = max(a, b, c), the terms added in this order; -inf for three -inf
+ *   alpha(0, 0) = lp(0, blank),  alpha(0, 1) = lp(0, e(1)),  alpha(0, s > 1) = -inf
+ *   alpha(t, s) = lp(t, e(s)) + lse3(alpha(t - 1, s), alpha(t - 1, s - 1), skip(s) ? alpha(t - 1, s - 2) : -inf)
+ *   log p       = logaddexp(alpha(n_steps - 1, S - 1), alpha(n_steps - 1, S - 2))     (K28's logaddexp; the second -inf when S = 1)
+ *   beta(n_steps - 1, s) = 0 for s = S - 1 and s = S - 2, -inf otherwise
+ *   c(t + 1, s) = lp(t + 1, e(s)) + beta(t + 1, s)
+ *   beta(t, s)  = lse3(c(t + 1, s), c(t + 1, s + 1), skip(s + 2) ? c(t + 1, s + 2) : -inf)      states at or past S count -inf
+ *   gamma(t, s) = exp((alpha(t, s) + beta(t, s)) - log p)
+ *   post(t, v)  = sum of gamma(t, s) over the states with e(s) = v: for a label class in order of s, starting from 0; for the blank
+ *                 lane i adds gamma(t, 2 i) + gamma(t, 2 (i + 64)) (a state at or past S counts 0), then the butterfly of dx_wave_sum
+ *   grad(t, v)  = w[b] * (exp(x(t, v) - z(t)) - post(t, v))   for t < n_steps;  0 for t >= n_steps
+ * status[b]: 2 when n_steps[b] == 0; otherwise 3 when one of the word's labels is outside [1, V - 1]; otherwise 1 when
+ * n_steps[b] < n_labels[b] + (number of u >= 1 with labels[u] == labels[u - 1]) (no path: equal neighbours need a blank between);
+ * otherwise 0.  n_labels[b] == 0 is a valid word (the all-blank path).  status != 0: loss NaN, the word's grad all 0.
+ * ws: B * T * (2 U + 1) floats of scratch (the alpha plane: T x S floats per word do not fit LDS beside the other words of a
+ * workgroup).  Nothing in it has to be initialised or to survive the call; a lane reads back only cells it wrote in this call.
+ *
+ * dx_ctc_greedy (generate.py:84-105): -> ids (B, T) int32, n_out (B) int32, score (B) fp32.
+ *   best(t)  = the class of the largest x(t, .), the LOWEST class among equal ones
+ *   ids[b]   = best(0 .. n_steps - 1) with runs of one class collapsed to one entry, then the blanks dropped; n_out[b] entries,
+ *              0 behind them up to T
+ *   score[b] = sum over t, in order, of -log(sum_v exp(x(t, v) - max_v x(t, v)))  = sum_t max_v lp(t, v);  0 for n_steps = 0
+ *
+ * Both kernels: one wave per word, four words per workgroup, no barrier.  The loss kernel holds K = 1, 2 or 4 consecutive states per
+ * lane (2 U + 1 <= 64 / 128 / 256); s - 1 and s - 2 are the lane's own registers or one DPP move away; emissions are gathered 8 (K = 1)
+ * or 4 steps ahead of the chain.  Sort a batch by n_steps so the waves of a workgroup end together. */
+long dx_ctc_max_steps(void);
+long dx_ctc_max_labels(void);
+long dx_ctc_max_classes(void);
+int dx_ctc_loss(const float* logits, const int64_t* n_steps, const int64_t* labels, const int64_t* n_labels, const float* w, float* loss,
+                int* status, float* grad, float* ws, int B, int T, int U, int V, void* stream);
+int dx_ctc_greedy(const float* logits, const int64_t* n_steps, int* ids, int* n_out, float* score, int B, int T, int V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

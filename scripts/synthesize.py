@@ -1,9 +1,13 @@
 #!/usr/bin/env python
 """Batched prosody-transfer synthesis with objective scores, behind the flags of the reference's `scripts/synthesize.py`:
     python scripts/synthesize.py -out OUT_DIR -chk CHECKPOINT -tf SENTENCES -sb STYLE_BANK [-bs N] [-rtf] [-ctrl] [-voc G_CKPT [-vcfg JSON]]
+                                 [-dict DICTIONARY [-g2p G2P_CKPT]]
 
   -tf   phonemised sentences, one `file_name|{P1 P2} {P3} , {P4} ? ~` per line: the `sentences_to_generate.txt` the reference
-        writes after text cleaning and MFA g2p, which stay outside this project (`generate.read_phonemised_sentences`)
+        writes after text cleaning and g2p (`generate.read_phonemised_sentences`); with -dict: raw text, one sentence per line
+  -dict a pronunciation dictionary (`word P1 P2 ...` per line): -tf is then RAW text, which is cleaned, looked up and written to
+        `<out>/sentences_to_generate.txt` first (`generate.prepare_sentences_for_inference`); -g2p: the model of
+        `scripts/train_g2p.py` for the words the dictionary lacks (without it such a word is an error)
   -sb   directory of reference `.wav` files; each gets its `.npz` of energy, pitch and mel-spectrogram beside it, extracted on
         the GPU as one batch
   -rtf  an extra pass without audio that logs the real-time factor at this batch size
@@ -75,6 +79,21 @@ def load_vocoder(checkpoint, config, hparams):
     vocoder = Vocoder.from_checkpoint(checkpoint, config, compute_dtype=hparams.compute_dtype, device='cuda:0')
     vocoder.check_hparams(hparams)
     return vocoder
+
+
+def phonemise(args, hparams):
+    ''' -dict: the raw text of -tf to `<out>/sentences_to_generate.txt`, which then takes the place of -tf '''
+    from daft_exprt.text import load_dictionary
+    g2p = None
+    if args.g2p is not None:
+        from daft_exprt.g2p import load_g2p
+        g2p = load_g2p(args.g2p)
+    found = {}
+    generate.prepare_sentences_for_inference(args.text_file, args.output_dir, hparams, g2p=g2p,
+                                             dictionary=load_dictionary(args.dictionary, hparams.symbols), report=found)
+    for word, phones in sorted(found['oov'].items()):
+        _logger.info(f'not in the dictionary: "{word}" -> {" ".join(phones)}')
+    args.text_file = os.path.join(args.output_dir, 'sentences_to_generate.txt')
 
 
 def run(args, model, hparams, control=None, audio=True, scores=None, vocoder=None):
@@ -161,11 +180,17 @@ def main():
     parser.add_argument('-ctrl', '--control', action='store_true', help='apply the duration x 1.25, pitch + 50 Hz example to every symbol')
     parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN generator checkpoint: write and score its audio instead of the Griffin-Lim preview')
     parser.add_argument('-vcfg', '--vocoder_config', default=None, help='HiFi-GAN config.json (default: beside the vocoder checkpoint)')
+    parser.add_argument('-dict', '--dictionary', default=None, help='pronunciation dictionary: -tf is then raw text and is phonemised first')
+    parser.add_argument('-g2p', '--g2p', default=None, help='g2p model (scripts/train_g2p.py) for the words the dictionary lacks; needs -dict')
     args = parser.parse_args()
+    if args.g2p is not None and args.dictionary is None:
+        parser.error('-g2p needs -dict')
     logging.basicConfig(format='%(asctime)s [%(levelname)s] %(message)s', datefmt='%Y-%m-%d %H:%M:%S', level=logging.INFO)
     random.seed(1234)
 
     model, hparams = load_model(args.checkpoint)
+    if args.dictionary is not None:
+        phonemise(args, hparams)
     vocoder = load_vocoder(args.vocoder, args.vocoder_config, hparams) if args.vocoder else None
     if args.real_time_factor:
         run(args, model, hparams, audio=False)

@@ -5,9 +5,11 @@ per-symbol duration / energy / pitch control factors, reference `.npz` prosody, 
 `generate_batch_mel_specs` (242-317: one `model.inference` call per batch, crop per item, `.npz` with the same keys,
 Griffin-Lim preview `.wav` per item on the GPU, `daft_exprt/griffin_lim.py`, or HiFi-GAN audio, `daft_exprt/vocoder.py`) and `generate_mel_specs` (320-437: chunking +
 real-time-factor accounting) and `extract_reference_parameters` (440-462: a reference recording -> the `.npz` of energy, pitch
-and mel-spectrogram the collate reads; wav reading, resampling, pitch and mel all on the GPU).  Text phonemisation (MFA g2p) and plots are outside the accelerated path (SURVEY 2, rows
-6/13/15): sentences arrive phonemised --
-a list of words (lists of phone symbols) and boundary symbols, exactly what `prepare_sentences_for_inference` returns.
+and mel-spectrogram the collate reads; wav reading, resampling, pitch and mel all on the GPU).  Plots are outside the accelerated
+path.  The drivers here take sentences phonemised -- a list of words (lists of phone symbols) and boundary
+symbols, exactly what `prepare_sentences_for_inference` returns; `phonemize_sentence` and `prepare_sentences_for_inference`
+(28-107, 465-494) are those of `daft_exprt/text.py`, re-exported here under the reference's import path: a dictionary lookup, and a
+g2p model trained on that dictionary (`daft_exprt/g2p.py`) in place of `mfa g2p`.
 """
 import logging
 import os
@@ -20,6 +22,7 @@ import torch
 from daft_exprt import _hip as H
 from daft_exprt import audio, evaluate, griffin_lim
 from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
+from daft_exprt.text import phonemize_sentence, prepare_sentences_for_inference  # noqa: F401
 from daft_exprt.vocoder import pcm16
 
 _logger = logging.getLogger(__name__)
