@@ -24,28 +24,19 @@ import numpy as np
 import torch
 
 from daft_exprt import _hip as H
+from daft_exprt.evaluate import dtw_align_batch, max_dtw_length, mel_cepstrum_batch
+from daft_exprt.extract_features import sentence_tokens
+from daft_exprt.generate import _symbol_ids, read_phonemised_sentences
+from daft_exprt.recordings import ALIGN_KEYS, _parameters_of, active_span_batch, copy_inference, empty_alignment  # noqa: F401
+from daft_exprt.recordings import load_recordings, pad_references, phonemised_by_speaker, sounding_crops, write_early_statuses
 from daft_exprt.symbols import SIL_PHONE_SYMBOL, SIL_WORD_SYMBOL, punctuation
+from daft_exprt.write_behind import WriteBehind
 
 _logger = logging.getLogger(__name__)
 
 STATUS = {0: 'ok', 1: 'the recording has fewer frames than its sounding symbols need',
           2: 'the synthesis gave nothing to transfer', 3: 'longer than the DTW takes',
           4: 'the sounding stretch is shorter than the analysis window'}
-
-
-def active_span_batch(energy, n_frames, rel_db=-40.0):
-    ''' `dx_active_span`: energy (B, T) fp32 and n_frames (B,) int64 on the device -> (begin, end) (B,) int64: the first frame
-        whose energy reaches the row's peak * 10^(rel_db / 20) and one past the last; (0, 0) for an empty or all-zero row.
-        Nothing at or past n_frames[b] is read. '''
-    H.require_gpu(energy, n_frames)
-    assert energy.dtype == torch.float32 and energy.dim() == 2 and energy.stride(1) == 1 and n_frames.dtype == torch.int64
-    B, T = energy.shape
-    assert n_frames.shape == (B,)
-    begin = torch.empty((B,), dtype=torch.int64, device=energy.device)
-    end = torch.empty((B,), dtype=torch.int64, device=energy.device)
-    H.check(H.lib().dx_active_span(H.ptr(energy), energy.stride(0), H.ptr(n_frames.contiguous()), float(rel_db), H.ptr(begin),
-                                   H.ptr(end), B, T, H.stream()))
-    return begin, end
 
 
 def dtw_transfer_batch(path, path_len, n_ref, n_gen, gen_durations, n_symbols, min_frames):
@@ -62,7 +53,6 @@ def dtw_transfer_batch(path, path_len, n_ref, n_gen, gen_durations, n_symbols, m
     assert path.shape[0] == B and path_len.shape == (B,) and n_ref.shape == (B,) and n_gen.shape == (B,) and n_symbols.shape == (B,)
     # the kernel is told the extents the path was laid out for; their sum is what matters, so any split that holds the longest
     # row of either side will do (one read-back; `transfer_durations` knows the extents and reads nothing back)
-    from daft_exprt.evaluate import max_dtw_length
     T_ref = max(1, int(n_ref.max()), path.shape[1] + 1 - max_dtw_length())
     T_gen = path.shape[1] + 1 - T_ref
     if T_gen < max(1, int(n_gen.max())):
@@ -84,7 +74,6 @@ def _transfer(path, path_len, n_ref, n_gen, gen_durations, n_symbols, min_frames
 
 
 def _transfer_from_mels(mel_gen, n_gen, gen_durations, n_symbols, mel_rec, n_rec, min_frames, n_coeffs):
-    from daft_exprt.evaluate import dtw_align_batch, mel_cepstrum_batch
     cep_rec = mel_cepstrum_batch(mel_rec, n_rec, n_coeffs)
     cep_gen = mel_cepstrum_batch(mel_gen, n_gen, n_coeffs)
     total, path, path_len = dtw_align_batch(cep_rec, n_rec, cep_gen, n_gen)
@@ -102,16 +91,13 @@ def transfer_durations(mel_gen, n_gen, gen_durations, n_symbols, mel_rec, n_rec,
     return _transfer_from_mels(mel_gen, n_gen, gen_durations, n_symbols, mel_rec, n_rec, min_frames, n_coeffs)[:4]
 
 
-ALIGN_KEYS = ('begin', 'rec_durations', 'gen_durations', 'moved', 'status', 'path_cost', 'frames', 'frames_gen')
-
-
 def align_batch(model, symbols, input_lengths, wavs, n_samples, speaker_ids, hparams, min_frames=3, trim_db=-40.0):
     ''' symbols (B, L) / input_lengths (B,) / speaker_ids (B,) int64 and wavs (B, S) fp32 at hparams.sampling_rate on the device,
         n_samples: the B sample counts on the host.  Per utterance: the mel front-end's frame energies give the sounding stretch
-        [begin, end) (`active_span_batch`, trim_db below the peak), the recording is cropped to it, the crop's energy, pitch and
-        mel are both the prosody reference of a free-running synthesis (factors 1, pitch 'add' 0, as `evaluate.copy_synthesis`)
-        and the target its mel is warped onto (`transfer_durations`).  Returns {key: (B,) device tensor, the durations (B, L)} for
-        ALIGN_KEYS, rows in the caller's order:
+        [begin, end) (`recordings.sounding_crops`, trim_db below the peak), the recording is cropped to it, the crop's energy, pitch
+        and mel are both the prosody reference of a free-running synthesis (`recordings.copy_inference`, as
+        `evaluate.copy_synthesis`) and the target its mel is warped onto (`transfer_durations`).  Returns {key: (B,) device tensor,
+        the durations (B, L)} for ALIGN_KEYS, rows in the caller's order:
           begin          first frame of the crop in the recording (int64);  frames: the crop's frames;  frames_gen: the synthesis'
           rec_durations  frames of every symbol in the crop, summing to `frames` where status is 0 (int64)
           gen_durations  frames the model gave every symbol in its synthesis (int64)
@@ -119,72 +105,22 @@ def align_batch(model, symbols, input_lengths, wavs, n_samples, speaker_ids, hpa
                          decided before any launch; the synthesis': before the DTW), 4: a recording or a sounding stretch of no
                          more than filter_length / 2 samples.  rec_durations and moved are 0 where status != 0.
           path_cost      the DTW total divided by the path length (fp32; NaN where status is 3 or 4) '''
-    from daft_exprt.evaluate import max_dtw_length
-    from daft_exprt.extract_features import mel_spectrogram_batch, nb_frames, wav_crop_batch
-    from daft_exprt.generate import _parameters_of
     H.require_gpu(symbols, input_lengths, wavs, speaker_ids)
-    if not hparams.centered:
-        raise ValueError('align_batch: the pitch frames line up with the mel frames only with hparams.centered')
     dev = wavs.device
     B, L = symbols.shape
-    hop, half = int(hparams.hop_length), int(hparams.filter_length) // 2
-    n_samples = [int(n) for n in (n_samples.tolist() if torch.is_tensor(n_samples) else n_samples)]
-    limit = max_dtw_length()
-    out = {'begin': torch.zeros((B,), dtype=torch.int64, device=dev), 'rec_durations': torch.zeros((B, L), dtype=torch.int64, device=dev),
-           'gen_durations': torch.zeros((B, L), dtype=torch.int64, device=dev),
-           'moved': torch.zeros((B,), dtype=torch.int32, device=dev), 'status': torch.zeros((B,), dtype=torch.int32, device=dev),
-           'path_cost': torch.full((B,), float('nan'), dtype=torch.float32, device=dev),
-           'frames': torch.zeros((B,), dtype=torch.int64, device=dev), 'frames_gen': torch.zeros((B,), dtype=torch.int64, device=dev)}
-    status = [3 if nb_frames(n, hparams) > limit else 4 if n <= half else 0 for n in n_samples]
-    rows = [b for b in range(B) if status[b] == 0]
+    out = empty_alignment(B, L, dev)
     with torch.no_grad():
+        status, rows, begin, cropped, lengths, _ = sounding_crops(wavs, n_samples, hparams, trim_db)
         if rows:
             idx = torch.tensor(rows, dtype=torch.int64, device=dev)
-            n_dev = torch.tensor([n_samples[b] for b in rows], dtype=torch.int64, device=dev)
-            sub = wavs[idx][:, :max(n_samples[b] for b in rows)].contiguous()
-            _, energy, n_frames = mel_spectrogram_batch(sub, n_dev, hparams, min_samples=min(n_samples[b] for b in rows))
-            begin, end = active_span_batch(energy, n_frames, trim_db)
-            spans = torch.stack([begin, end], dim=1).cpu().tolist()
-            crops = {}
-            for b, (f0, f1) in zip(rows, spans):
-                first, last = f0 * hop, min(f1 * hop, n_samples[b])
-                if last - first <= half:
-                    status[b] = 4
-                else:
-                    crops[b] = (f0, first, last - first)
-            keep = [i for i, b in enumerate(rows) if b in crops]
-            rows = [rows[i] for i in keep]
-        if rows:
-            idx = torch.tensor(rows, dtype=torch.int64, device=dev)
-            lengths = [crops[b][2] for b in rows]
-            crop = torch.tensor([[crops[b][1], crops[b][2]] for b in rows], dtype=torch.int64, device=dev)
-            cropped = wav_crop_batch(sub[torch.tensor(keep, dtype=torch.int64, device=dev)].contiguous(), crop, max(lengths))
-            params = _parameters_of(cropped, lengths, hparams)
-            T = max(p[2].shape[1] for p in params)
-            n_mel = int(hparams.n_mel_channels)
-            energy_refs, pitch_refs = np.zeros((len(rows), T), dtype=np.float32), np.zeros((len(rows), T), dtype=np.float32)
-            mel_rec = np.zeros((len(rows), n_mel, T), dtype=np.float32)
-            for i, (e, p, m) in enumerate(params):
-                energy_refs[i, :len(e)], pitch_refs[i, :len(p)], mel_rec[i, :, :m.shape[1]] = e, p, m
-            n_rec = torch.tensor([p[2].shape[1] for p in params], dtype=torch.int64, device=dev)
-            energy_refs, pitch_refs, mel_rec = (torch.from_numpy(a).to(dev) for a in (energy_refs, pitch_refs, mel_rec))
-            # the model takes its batches in order of symbol count, longest first (the collates sort them so)
-            lens, order = torch.sort(input_lengths[idx], descending=True, stable=True)
-            back = torch.argsort(order)
-            sym = symbols[idx][order][:, :max(int(lens[0]), 1)].contiguous()
-            ones = torch.ones(sym.shape, dtype=torch.float32, device=dev)
-            core = model if hasattr(model, 'inference') else model.module
-            was_training = model.training
-            model.eval()
-            enc, (mel_gen, n_gen), _ = core.inference((sym, ones, ones, torch.zeros_like(ones), lens.contiguous(), energy_refs[order].contiguous(),
-                                                       pitch_refs[order].contiguous(), mel_rec[order].contiguous(), n_rec[order].contiguous(),
-                                                       speaker_ids[idx][order].contiguous()), 'add', hparams)
-            model.train(was_training)
-            mel_gen, n_gen = mel_gen.float()[back].contiguous(), n_gen.long()[back].contiguous()
+            energy_refs, pitch_refs, mel_rec, n_rec = pad_references(_parameters_of(cropped, lengths, hparams), dev)
+            enc, (mel_gen, n_gen), _, _ = copy_inference(model, symbols[idx], input_lengths[idx], energy_refs, pitch_refs, mel_rec, n_rec,
+                                                         speaker_ids[idx], hparams)
+            mel_gen, n_gen = mel_gen.float().contiguous(), n_gen.long().contiguous()
             gen_dur = torch.zeros((len(rows), L), dtype=torch.int64, device=dev)
-            gen_dur[:, :sym.shape[1]] = enc[1].long()[back]
+            gen_dur[:, :enc[1].shape[1]] = enc[1].long()
             # a synthesis longer than the DTW takes: status 3 as well
-            long_rows = [i for i, n in enumerate(n_gen.tolist()) if n > limit]
+            long_rows = [i for i, n in enumerate(n_gen.tolist()) if n > max_dtw_length()]
             for i in long_rows:
                 status[rows[i]] = 3
             fit = [i for i in range(len(rows)) if i not in set(long_rows)]
@@ -199,12 +135,9 @@ def align_batch(model, symbols, input_lengths, wavs, n_samples, speaker_ids, hpa
                 out['rec_durations'][to], out['moved'][to], out['status'][to] = rec, moved, st
                 out['gen_durations'][to] = gen_dur[sel]
                 out['path_cost'][to] = total / path_len.clamp(min=1).float()
-                out['begin'][to] = torch.tensor([crops[rows[i]][0] for i in fit], dtype=torch.int64, device=dev)
+                out['begin'][to] = torch.tensor([begin[i] for i in fit], dtype=torch.int64, device=dev)
                 out['frames'][to], out['frames_gen'][to] = n_rec[sel], n_gen_fit
-    early = [b for b in range(B) if status[b] != 0]
-    if early:
-        out['status'][torch.tensor(early, dtype=torch.int64, device=dev)] = torch.tensor([status[b] for b in early], dtype=torch.int32,
-                                                                                        device=dev)
+    write_early_statuses(out, status)
     return out
 
 
@@ -225,7 +158,6 @@ def flatten_sentence(sentence):
 
 def lab_words(lab_sentence):
     ''' the words of a .lab sentence as `extract_features.update_markers` will look for them in the markers '''
-    from daft_exprt.extract_features import sentence_tokens
     return [token for token in sentence_tokens(lab_sentence)[0] if token not in punctuation]
 
 
@@ -328,27 +260,20 @@ def align_data_set(dataset_dir, speakers, phonemised_files, model, hparams, batc
         for every speaker -- `<dataset_dir>/<speaker>/wavs/NAME.wav`, `<dataset_dir>/<speaker>/align/NAME.lab` and the `NAME|...`
         lines of the speaker's phonemised file (`generate.read_phonemised_sentences`; phonemised_files: {speaker: path}, a list
         in the order of `speakers`, or one path for all) -- writes `<dataset_dir>/<speaker>/align/NAME.markers` from
-        `align_batch`, batch_size utterances at a time: the wavs go to the device through `audio.device_waves`, the results come
+        `align_batch`, batch_size utterances at a time: the wavs go to the device through `recordings.load_recordings`, the results come
         back through `write_behind.WriteBehind`.  Existing .markers are kept unless `overwrite`.  The speaker id is the one
         `hparams.speakers_id` holds for the speaker.  An utterance without a wav or a .lab, whose .lab words are not as many as
         its phonemised words, or that ends with status != 0 or a phone without frames is skipped with a warning.
         Returns the report and writes it to report_file (default `<dataset_dir>/align_report.json`): {'files': {'speaker/NAME':
         {status, moved, path_cost, frames, frames_gen, symbols, written}}, 'summary': {...}, 'skipped': [[speaker, NAME, reason]],
         'already_done', 'batches', 'seconds', 'min_frames', 'trim_db'}. '''
-    from daft_exprt import audio
-    from daft_exprt.aligner import Aligner
-    from daft_exprt.generate import _symbol_ids, read_phonemised_sentences
-    from daft_exprt.write_behind import WriteBehind
+    from daft_exprt.aligner import Aligner     # (`aligner` imports this module for `dtw_transfer_batch`)
     dev = H.device(device)
     fs = int(hparams.sampling_rate)
     speakers = list(speakers)
     learned = isinstance(model, Aligner)     # a learned aligner (DESIGN 9l) knows no speakers: any name goes, the id is unused
     run = model.align_batch if learned else (lambda *a: align_batch(model, *a))
-    if isinstance(phonemised_files, (str, os.PathLike)):
-        phonemised_files = {speaker: phonemised_files for speaker in speakers}
-    elif not isinstance(phonemised_files, dict):
-        assert len(phonemised_files) == len(speakers), f'{len(phonemised_files)} phonemised files for {len(speakers)} speakers'
-        phonemised_files = dict(zip(speakers, phonemised_files))
+    phonemised_files = phonemised_by_speaker(phonemised_files, speakers)
     records, skipped = {}, []
     report = {'files': records, 'summary': {}, 'skipped': skipped, 'already_done': 0, 'batches': 0, 'seconds': 0.,
               'min_frames': int(min_frames), 'trim_db': float(trim_db)}
@@ -385,23 +310,11 @@ def align_data_set(dataset_dir, speakers, phonemised_files, model, hparams, batc
         try:
             for pos in range(0, len(todo), int(batch_size)):
                 utts = todo[pos: pos + int(batch_size)]
-                for u in utts:
-                    x, u.rate = audio.read_wav(u.wav_file)
-                    u.samples = audio.to_float_mono(x)
-                wavs, n_total = audio.device_waves(utts, fs, dev)
-                for u, n in zip(utts, n_total):
-                    u.n_samples = n
-                L = max(len(u.ids) for u in utts)
-                symbols = torch.zeros((len(utts), L), dtype=torch.int64)
-                for b, u in enumerate(utts):
-                    symbols[b, :len(u.ids)] = torch.tensor(u.ids, dtype=torch.int64)
-                ints = torch.tensor([[len(u.ids), speaker_id] for u in utts], dtype=torch.int64).to(dev)
-                out = run(symbols.to(dev), ints[:, 0].contiguous(), wavs, n_total, ints[:, 1].contiguous(), hparams, min_frames, trim_db)
+                symbols, (input_lengths, speaker_ids), wavs, n_total = load_recordings(utts, fs, dev, [(speaker_id,)] * len(utts))
+                out = run(symbols, input_lengths, wavs, n_total, speaker_ids, hparams, min_frames, trim_db)
                 named = [(key, out[key]) for key in ALIGN_KEYS]
                 layout = [(key, str(t.dtype).replace('torch.', ''), tuple(t.shape)) for key, t in named]
                 writer.put(torch.cat([t.contiguous().view(-1).view(torch.uint8) for _, t in named]), layout, utts)
-                for u in utts:
-                    u.samples = None
                 report['batches'] += 1
         finally:
             writer.close()

@@ -21,6 +21,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from daft_exprt import _hip as H
+from daft_exprt.align import dtw_transfer_batch
+from daft_exprt.extract_features import mel_spectrogram_batch
+from daft_exprt.generate import _symbol_ids, read_phonemised_sentences
+from daft_exprt.recordings import empty_alignment, load_recordings, phonemised_by_speaker, sounding_crops, write_early_statuses
 
 _logger = logging.getLogger(__name__)
 
@@ -163,7 +167,6 @@ def hard_durations(logp, n_frm, n_sym, min_frames=1):
     ''' MAS, then `align.dtw_transfer_batch` with every symbol sounding and one "synthesis" frame long (gen_durations all 1,
         n_gen = n_sym).  Returns (durations (B, L) int64: the frames of every symbol, at least min_frames each where status is 0;
         moved, status: as `dtw_transfer_batch`; score (B,) fp32 and mas_status (B,) int32 of `mas_path`) '''
-    from daft_exprt.align import dtw_transfer_batch
     path, path_len, score, mas_status = mas_path(logp, n_frm, n_sym)
     ones = torch.ones((logp.shape[0], logp.shape[2]), dtype=torch.int64, device=logp.device)
     durations, moved, status = dtw_transfer_batch(path, path_len, n_frm.contiguous(), n_sym.contiguous(), ones, n_sym.contiguous(),
@@ -218,11 +221,7 @@ class Aligner(nn.Module):
         H.require_gpu(symbols, input_lengths, wavs)
         dev = wavs.device
         B, L = symbols.shape
-        out = {'begin': torch.zeros((B,), dtype=torch.int64, device=dev), 'rec_durations': torch.zeros((B, L), dtype=torch.int64, device=dev),
-               'gen_durations': torch.zeros((B, L), dtype=torch.int64, device=dev),
-               'moved': torch.zeros((B,), dtype=torch.int32, device=dev), 'status': torch.zeros((B,), dtype=torch.int32, device=dev),
-               'path_cost': torch.full((B,), float('nan'), dtype=torch.float32, device=dev),
-               'frames': torch.zeros((B,), dtype=torch.int64, device=dev), 'frames_gen': torch.zeros((B,), dtype=torch.int64, device=dev)}
+        out = empty_alignment(B, L, dev)
         with torch.no_grad():                                     # (no dropout or norm layer: nothing depends on the training mode)
             status, rows, begin, mel, n_rec = sounding_mels(wavs, n_samples, hparams, trim_db)
             if rows:
@@ -238,52 +237,18 @@ class Aligner(nn.Module):
                 out['path_cost'][idx] = -score / n_rec.clamp(min=1).float()
                 out['begin'][idx] = torch.tensor(begin, dtype=torch.int64, device=dev)
                 out['frames'][idx], out['frames_gen'][idx] = n_rec, n_sym
-        early = [b for b in range(B) if status[b] != 0]
-        if early:
-            out['status'][torch.tensor(early, dtype=torch.int64, device=dev)] = torch.tensor([status[b] for b in early], dtype=torch.int32,
-                                                                                            device=dev)
+        write_early_statuses(out, status)
         return out
 
 
 def sounding_mels(wavs, n_samples, hparams, trim_db=-40.0):
-    ''' the front end of `align.align_batch`: wavs (B, S) fp32 at hparams.sampling_rate on the device, n_samples: the B sample
-        counts on the host.  Returns (status: B host ints, 3 more frames than `evaluate.max_dtw_length()`, 4 a recording or a
-        sounding stretch of no more than filter_length / 2 samples, else 0;  rows: the b with status 0;  begin: the first frame of
-        their crops;  mel (len(rows), n_mel, T) fp32 natural-log mel of the crops and n_rec (len(rows),) int64 their frames) '''
-    from daft_exprt.align import active_span_batch
-    from daft_exprt.evaluate import max_dtw_length
-    from daft_exprt.extract_features import mel_spectrogram_batch, nb_frames, wav_crop_batch
-    if not hparams.centered:
-        raise ValueError('sounding_mels: the frames [begin, end) are cut at hop multiples only with hparams.centered')
-    dev = wavs.device
-    hop, half = int(hparams.hop_length), int(hparams.filter_length) // 2
-    n_samples = [int(n) for n in (n_samples.tolist() if torch.is_tensor(n_samples) else n_samples)]
-    limit = max_dtw_length()
-    status = [3 if nb_frames(n, hparams) > limit else 4 if n <= half else 0 for n in n_samples]
-    rows = [b for b in range(len(n_samples)) if status[b] == 0]
+    ''' the front end of `align.align_batch` (`recordings.sounding_crops`: its arguments, status, rows and begin) and the crops'
+        natural-log mel (len(rows), n_mel, T) fp32 with n_rec (len(rows),) int64, their frames '''
+    status, rows, begin, cropped, lengths, crop = sounding_crops(wavs, n_samples, hparams, trim_db)
     if not rows:
         return status, [], [], None, None
-    idx = torch.tensor(rows, dtype=torch.int64, device=dev)
-    n_dev = torch.tensor([n_samples[b] for b in rows], dtype=torch.int64, device=dev)
-    sub = wavs[idx][:, :max(n_samples[b] for b in rows)].contiguous()
-    _, energy, n_frames = mel_spectrogram_batch(sub, n_dev, hparams, min_samples=min(n_samples[b] for b in rows))
-    begin, end = active_span_batch(energy, n_frames, trim_db)
-    crops = {}
-    for b, (f0, f1) in zip(rows, torch.stack([begin, end], dim=1).cpu().tolist()):
-        first, last = f0 * hop, min(f1 * hop, n_samples[b])
-        if last - first <= half:
-            status[b] = 4
-        else:
-            crops[b] = (f0, first, last - first)
-    keep = [i for i, b in enumerate(rows) if b in crops]
-    rows = [rows[i] for i in keep]
-    if not rows:
-        return status, [], [], None, None
-    lengths = [crops[b][2] for b in rows]
-    crop = torch.tensor([[crops[b][1], crops[b][2]] for b in rows], dtype=torch.int64, device=dev)
-    cropped = wav_crop_batch(sub[torch.tensor(keep, dtype=torch.int64, device=dev)].contiguous(), crop, max(lengths))
     mel, _, n_rec = mel_spectrogram_batch(cropped, crop[:, 1].contiguous(), hparams, min_samples=min(lengths))
-    return status, rows, [crops[b][0] for b in rows], mel, n_rec
+    return status, rows, begin, mel, n_rec
 
 
 # ---- training and checkpoints ----------------------------------------------------------------------------------------------------------
@@ -326,19 +291,13 @@ def train_aligner(dataset_dir, speakers, phonemised_files, hparams, steps=2000, 
                   prior_sigma=0.2, seed=1234, hidden=256, att_dim=80, trim_db=-40.0, log_every=100, device='cuda:0'):
     ''' trains an `Aligner` on the recordings `align.align_data_set` reads -- `<dataset_dir>/<speaker>/wavs/NAME.wav` for the
         `NAME|...` lines of the speaker's phonemised file (phonemised_files as there) -- and returns it.  The mels of the sounding
-        stretches are extracted once, batch_size recordings at a time through `audio.device_waves` and `sounding_mels`, and stay
-        on the device; every step draws batch_size of them (a seeded permutation per step), Adam at `lr`, the loss logged every
+        stretches are extracted once, batch_size recordings at a time through `recordings.load_recordings` and `sounding_mels`, and
+        stay on the device; every step draws batch_size of them (a seeded permutation per step), Adam at `lr`, the loss logged every
         `log_every` steps.  Recordings without a wav, with status 3 / 4 or with fewer frames than symbols are left out. '''
-    from daft_exprt import audio
-    from daft_exprt.generate import _symbol_ids, read_phonemised_sentences
     dev = H.device(device)
     fs = int(hparams.sampling_rate)
     speakers = list(speakers)
-    if isinstance(phonemised_files, (str, os.PathLike)):
-        phonemised_files = {speaker: phonemised_files for speaker in speakers}
-    elif not isinstance(phonemised_files, dict):
-        assert len(phonemised_files) == len(speakers), f'{len(phonemised_files)} phonemised files for {len(speakers)} speakers'
-        phonemised_files = dict(zip(speakers, phonemised_files))
+    phonemised_files = phonemised_by_speaker(phonemised_files, speakers)
     items, left_out = [], 0
     for speaker in speakers:
         wavs_dir = os.path.join(dataset_dir, speaker, 'wavs')
@@ -351,18 +310,13 @@ def train_aligner(dataset_dir, speakers, phonemised_files, hparams, steps=2000, 
         todo = [u for u in todo if os.path.isfile(u.wav_file)]
         for pos in range(0, len(todo), int(batch_size)):
             utts = todo[pos: pos + int(batch_size)]
-            for u in utts:
-                x, u.rate = audio.read_wav(u.wav_file)
-                u.samples = audio.to_float_mono(x)
-            wavs, n_total = audio.device_waves(utts, fs, dev)
+            symbols, _, wavs, n_total = load_recordings(utts, fs, dev)
             with torch.no_grad():
                 status, rows, _, mel, n_rec = sounding_mels(wavs, n_total, hparams, trim_db)
             frames = n_rec.tolist() if rows else []
             for i, b in enumerate(rows):
                 if len(utts[b].ids) <= frames[i] and 0 < len(utts[b].ids) <= max_symbols():
-                    items.append((torch.tensor(utts[b].ids, dtype=torch.int64, device=dev), mel[i, :, :frames[i]].clone()))
-            for u in utts:
-                u.samples = None
+                    items.append((symbols[b, :len(utts[b].ids)].clone(), mel[i, :, :frames[i]].clone()))
         left_out += len(todo)
     left_out -= len(items)
     if not items:

@@ -22,12 +22,19 @@ import json
 import logging
 import math
 import os
+import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from daft_exprt import _hip as H
-from daft_exprt import ops
+from daft_exprt import audio, evaluate, griffin_lim, ops
+from daft_exprt.align import STATUS, align_batch
+from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
+from daft_exprt.generate import _symbol_ids
+from daft_exprt.recordings import _parameters_of, copy_inference, load_recordings, pad_references, sounding_crops, unwrap
+from daft_exprt.vocoder import pcm16
 
 _logger = logging.getLogger(__name__)
 
@@ -199,7 +206,6 @@ def _speaker_stats(hparams, speaker_ids, feature, device):
 
 
 def _align(obj, *args):
-    from daft_exprt.align import align_batch
     return obj.align_batch(*args) if hasattr(obj, 'align_batch') else align_batch(obj, *args)
 
 
@@ -221,9 +227,6 @@ def targets_from_recordings(aligner_or_model, symbols, input_lengths, wavs, n_sa
         sounding stretch analysed on its own, i.e. the recording as utterance-level prosody reference -- for a row with status != 0
         the whole recording, untrimmed, with zeros behind it up to one analysis window: a reference to synthesise it free-running
         with; usable (B,) bool: the rows whose targets carry weight}. '''
-    from daft_exprt.align import active_span_batch
-    from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch, wav_crop_batch
-    from daft_exprt.generate import _parameters_of
     if normalise not in NORMALISE:
         raise ValueError(f'normalise = {normalise!r} (one of {NORMALISE})')
     if normalise == 'target' and target_speaker_ids is None:
@@ -231,8 +234,6 @@ def targets_from_recordings(aligner_or_model, symbols, input_lengths, wavs, n_sa
     H.require_gpu(symbols, input_lengths, wavs, speaker_ids)
     dev = wavs.device
     B, L = symbols.shape
-    hop = int(hparams.hop_length)
-    n_mel = int(hparams.n_mel_channels)
     n_samples = [int(n) for n in (n_samples.tolist() if torch.is_tensor(n_samples) else n_samples)]
     with torch.no_grad():
         out = _align(aligner_or_model, symbols, input_lengths, wavs, n_samples, speaker_ids, hparams, min_frames, trim_db)
@@ -260,30 +261,21 @@ def targets_from_recordings(aligner_or_model, symbols, input_lengths, wavs, n_sa
             e, p, ss, dr, ps = ops.clone_pool(energy[:, :T], log_pitch[:, :T], out['begin'][idx].contiguous(),
                                               out['rec_durations'][idx].contiguous(), input_lengths[idx].contiguous(), pairs[0], pairs[1])
             sym_energy[idx], sym_pitch[idx], self_stats[idx], dropped[idx], pool_status[idx] = e, p, ss, dr, ps
-            # the sounding stretch on its own, as `align.align_batch` analysed it: the utterance-level reference
-            begin, end = active_span_batch(energy, n_frames, trim_db)
-            spans = torch.stack([begin, end], dim=1).cpu().tolist()
-            crop = [[f0 * hop, min(f1 * hop, n) - f0 * hop] for (f0, f1), n in zip(spans, sub_n)]
-            lengths = [c[1] for c in crop]
-            cropped = wav_crop_batch(sub, torch.tensor(crop, dtype=torch.int64, device=dev), max(lengths))
-            refs = dict(zip(rows, _parameters_of(cropped, lengths, hparams)))
+            # the sounding stretch on its own, as `align_batch` analysed it (the same front end on these energies): the utterance's reference
+            _, kept, _, cropped, lengths, _ = sounding_crops(sub, sub_n, hparams, trim_db, energy, n_frames)
+            if kept:
+                refs = dict(zip([rows[i] for i in kept], _parameters_of(cropped, lengths, hparams)))
         # a row that was not aligned still needs a reference to be synthesised free-running: its whole recording, untrimmed, with
         # zeros behind it up to one analysis window where it is shorter than that
-        rest = [b for b in range(B) if status[b] != 0]
+        rest = [b for b in range(B) if b not in refs]
         if rest:
             lengths = [max(n_samples[b], int(hparams.filter_length)) for b in rest]
             whole = torch.zeros((len(rest), max(lengths)), dtype=torch.float32, device=dev)
             for i, b in enumerate(rest):
                 whole[i, :n_samples[b]] = wavs[b, :n_samples[b]]
             refs.update(zip(rest, _parameters_of(whole, lengths, hparams)))
-        T_ref = max(r[2].shape[1] for r in refs.values())
-        energy_refs, pitch_refs = np.zeros((B, T_ref), dtype=np.float32), np.zeros((B, T_ref), dtype=np.float32)
-        mel = np.zeros((B, n_mel, T_ref), dtype=np.float32)
-        n_rec = np.zeros((B,), dtype=np.int64)
-        for b, (e, p, m) in refs.items():
-            energy_refs[b, :len(e)], pitch_refs[b, :len(p)], mel[b, :, :m.shape[1]], n_rec[b] = e, p, m, m.shape[1]
-        info.update(energy_refs=torch.from_numpy(energy_refs).to(dev), pitch_refs=torch.from_numpy(pitch_refs).to(dev),
-                    mel=torch.from_numpy(mel).to(dev), n_rec=torch.from_numpy(n_rec).to(dev), dropped=dropped, self_stats=self_stats,
+        energy_refs, pitch_refs, mel, n_rec = pad_references([refs[b] for b in range(B)], dev)
+        info.update(energy_refs=energy_refs, pitch_refs=pitch_refs, mel=mel, n_rec=n_rec, dropped=dropped, self_stats=self_stats,
                     pool_status=pool_status)
         usable = (out['status'] == 0) & (pool_status == 0) & (info['n_rec'] == out['frames'])
         ones = usable[:, None].expand(B, L).to(torch.float32)
@@ -324,8 +316,6 @@ def clone_batch(model, symbols, input_lengths, wavs, n_samples, speaker_ids, tar
           targets, info: as `targets_from_recordings` returns them (targets before `what` / `weights`).
         seconds: a dict that receives the wall time of the stages 'alignment + pooling', 'second pass', 'audio + scores' (each ends
         with a device synchronisation, so pass it only to measure). '''
-    import time
-    from daft_exprt import evaluate, griffin_lim
     H.require_gpu(symbols, input_lengths, wavs, speaker_ids, target_speaker_ids)
     dev = wavs.device
     B, L = symbols.shape
@@ -342,25 +332,13 @@ def clone_batch(model, symbols, input_lengths, wavs, n_samples, speaker_ids, tar
                                             min_frames, trim_db)
     clock = lap('alignment + pooling', clock)
     imposed = targets.select(what).scaled(weights)
-    core = model if hasattr(model, 'inference') else model.module
     with torch.no_grad():
-        # the model takes its batches in order of symbol count, longest first (the collates sort them so)
-        lens, order = torch.sort(input_lengths, descending=True, stable=True)
-        back = torch.argsort(order)
-        width = max(int(lens[0]), 1)
-        sym = symbols[order][:, :width].contiguous()
-        ones = torch.ones(sym.shape, dtype=torch.float32, device=dev)
-        src = order
-        was_training = model.training
-        model.eval()
-        enc, (mel, n_frames), _ = core.inference((sym, ones, ones, torch.zeros_like(ones), lens.contiguous(), info['energy_refs'][src].contiguous(),
-                                                  info['pitch_refs'][src].contiguous(), info['mel'][src].contiguous(), info['n_rec'][src].contiguous(),
-                                                  target_speaker_ids[order].contiguous()), 'add', hparams,
-                                                 prosody_targets=imposed.permute(order.cpu()).narrow(width))
-        model.train(was_training)
-        exact = (core.last_frame_exact[back] == 1) & info['usable']
-        mel, n_frames = mel.float()[back].contiguous(), n_frames.long()[back].contiguous()
-        wide = lambda t, dtype: torch.cat([t[back].to(dtype), torch.zeros((B, L - width), dtype=dtype, device=dev)], dim=1)
+        enc, (mel, n_frames), _, order = copy_inference(model, symbols, input_lengths, info['energy_refs'], info['pitch_refs'], info['mel'],
+                                                        info['n_rec'], target_speaker_ids, hparams, prosody_targets=imposed)
+        exact = unwrap(model).last_frame_exact                    # (in the order `inference` saw the rows in)
+        exact = ((exact if order is None else exact[torch.argsort(order)]) == 1) & info['usable']
+        mel, n_frames = mel.float().contiguous(), n_frames.long().contiguous()
+        wide = lambda t, dtype: torch.cat([t.to(dtype), torch.zeros((B, L - t.shape[1]), dtype=dtype, device=dev)], dim=1)
         result = {'mel': mel, 'n_frames': n_frames, 'dur': wide(enc[0], torch.float32), 'dur_int': wide(enc[1], torch.int64),
                   'energy': wide(enc[2], torch.float32), 'pitch': wide(enc[3], torch.float32), 'frame_exact': exact,
                   'targets': targets, 'info': info, 'wavs': None, 'n_samples': None}
@@ -383,7 +361,6 @@ def clone_batch(model, symbols, input_lengths, wavs, n_samples, speaker_ids, tar
         else:
             audio = None
         if audio is not None:
-            from daft_exprt.extract_features import pitch_batch
             result['wavs'], result['n_samples'] = audio, n_audio
             pcc = evaluate.prosody_transfer_scores(audio, n_audio, info['pitch_refs'], info['energy_refs'], info['n_rec'], hparams)
             for key in ('pitch_pcc', 'energy_pcc'):
@@ -415,7 +392,6 @@ def clone_report(names, host):
         `usable` false says the file was synthesised free-running; the reason is `status` (the alignment's), else `pool_status` 1 (the
         aligned rows overran the recording's curves), else the re-analysed sounding stretch had another frame count than the
         alignment's `frames`.  NaN is written as null, the means run over the files where the score is defined. '''
-    from daft_exprt.align import STATUS
     files = {}
     for b, name in enumerate(names):
         files[name] = {'status': int(host['status'][b]), 'frames': int(host['frames'][b]), 'begin': int(host['begin'][b]),
@@ -451,10 +427,6 @@ def clone_files(model, sentences, names, wav_files, target_speaker_ids, output_d
         `<output_dir>/<name>.npz` (key mel_spec) and `<name>.wav` as `generate.generate_batch_mel_specs` does (the vocoder's audio
         as 16-bit PCM, the Griffin-Lim preview as 64-bit float) and `<output_dir>/clone_report.json` (`clone_report`).  Returns
         the report. '''
-    from types import SimpleNamespace
-    from daft_exprt import audio
-    from daft_exprt.generate import _symbol_ids
-    from daft_exprt.vocoder import pcm16
     dev = H.device(device)
     fs = int(hparams.sampling_rate)
     n = len(sentences)
@@ -466,19 +438,12 @@ def clone_files(model, sentences, names, wav_files, target_speaker_ids, output_d
     reports = []
     for pos in range(0, n, int(batch_size)):
         sl = slice(pos, pos + int(batch_size))
-        utts = []
-        for path in wav_files[sl]:
-            x, rate = audio.read_wav(path)
-            utts.append(SimpleNamespace(samples=audio.to_float_mono(x), rate=rate))
-        wavs, n_total = audio.device_waves(utts, fs, dev)
-        ids = [_symbol_ids(s, hparams) for s in sentences[sl]]
-        symbols = torch.zeros((len(ids), max(len(i) for i in ids)), dtype=torch.int64)
-        for b, i in enumerate(ids):
-            symbols[b, :len(i)] = torch.tensor(i, dtype=torch.int64)
-        ints = torch.tensor([[len(i), s, t] for i, s, t in zip(ids, source_speaker_ids[sl], target_speaker_ids[sl])], dtype=torch.int64).to(dev)
-        out = clone_batch(model, symbols.to(dev), ints[:, 0].contiguous(), wavs, n_total, ints[:, 1].contiguous(), ints[:, 2].contiguous(),
-                          hparams, aligner=aligner, what=what, normalise=normalise, vocoder=vocoder,
-                          use_griffin_lim=use_griffin_lim and vocoder is None, min_frames=min_frames, trim_db=trim_db)
+        utts = [SimpleNamespace(wav_file=path, ids=_symbol_ids(s, hparams)) for path, s in zip(wav_files[sl], sentences[sl])]
+        symbols, (input_lengths, source, target), wavs, n_total = load_recordings(utts, fs, dev, list(zip(source_speaker_ids[sl],
+                                                                                                         target_speaker_ids[sl])))
+        out = clone_batch(model, symbols, input_lengths, wavs, n_total, source, target, hparams, aligner=aligner, what=what,
+                          normalise=normalise, vocoder=vocoder, use_griffin_lim=use_griffin_lim and vocoder is None, min_frames=min_frames,
+                          trim_db=trim_db)
         host = {key: out['info'][key].cpu().numpy() for key in INFO_KEYS}
         host['frame_exact'] = out['frame_exact'].cpu().numpy()
         host.update({key: out['scores'][key].cpu().numpy() for key in SCORE_KEYS})

@@ -20,7 +20,9 @@ import numpy as np
 import torch
 
 from daft_exprt import _hip as H
-from daft_exprt import config
+from daft_exprt import config, griffin_lim
+from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
+from daft_exprt.recordings import copy_inference, max_dtw_length, unwrap
 
 
 def max_curve_length():
@@ -73,7 +75,6 @@ def prosody_transfer_scores(wavs, n_samples, pitch_refs, energy_refs, ref_length
         `mel_spectrogram_batch`), then two `curve_pcc_batch` calls: pitch without the unvoiced frames, energy over all frames.
         Returns {key: (B,) device tensor} for SCORE_KEYS: the two correlations (fp32, NaN where undefined), the voiced frames
         of reference and generated pitch, the frames of reference and generated utterance. '''
-    from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
     H.require_gpu(wavs, n_samples, pitch_refs, energy_refs, ref_lengths)
     pitch, n_pitch = pitch_batch(wavs, n_samples, hparams)
     _, energy, n_frames = mel_spectrogram_batch(wavs, n_samples, hparams)
@@ -92,11 +93,6 @@ DTW_KEYS = ('mcd_db', 'f0_rmse_cents', 'vuv_error', 'voiced_pairs', 'path_len', 
 COPY_LEVELS = ('mel', 'audio')
 DTW_WORKSPACE_BYTES = 256 << 20         # default cap of the direction workspace: 256 pairs of 1000 x 1000 frames take 64 MB
 _DTW_WORKSPACE = {}                     # device -> grow-only byte tensor, kept across calls
-
-
-def max_dtw_length():
-    ''' longest sequence (frames) `dtw_align_batch` takes '''
-    return int(H.lib().dx_dtw_max_len())
 
 
 def _dct_table(n_mel, n_coeffs, device):
@@ -215,24 +211,17 @@ def copy_synthesis(model, batch, hparams, vocoder=None):
         transform 'add' with factor 0.  Returns (inputs of `parse_batch`, mel (B, n_mel, T) fp32, n_frames (B,) int64,
         wavs (B, S) fp32, n_samples (B,) int64): the decoder's mel and the waveform `vocoder` -- `griffin_lim_batch` when None --
         makes of it. '''
-    from daft_exprt import griffin_lim
     dev = next(model.parameters()).device
-    core = model if hasattr(model, 'inference') else model.module
-    inputs, _, _ = core.parse_batch(dev, batch)
-    symbols, input_lengths, frames_energy, frames_pitch, mel_specs, output_lengths, speaker_ids = (inputs[k] for k in (0, 5, 6, 7, 8, 9, 10))
-    ones = torch.ones(symbols.shape, dtype=torch.float32, device=dev)
-    was_training = model.training
-    model.eval()
+    inputs, _, _ = unwrap(model).parse_batch(dev, batch)
+    # symbols, input_lengths, frames_energy, frames_pitch, mel_specs, output_lengths, speaker_ids (the collate has sorted the batch)
+    _, (mel, n_frames), _, _ = copy_inference(model, *(inputs[k] for k in (0, 5, 6, 7, 8, 9, 10)), hparams)
     with torch.no_grad():
-        _, (mel, n_frames), _ = core.inference((symbols, ones, ones, torch.zeros_like(ones), input_lengths, frames_energy, frames_pitch,
-                                                 mel_specs, output_lengths, speaker_ids), 'add', hparams)
         mel, n_frames = mel.float().contiguous(), n_frames.long()
         if vocoder is not None:
             vocoder.check_hparams(hparams)
             wavs, n_samples = vocoder(mel, n_frames)
         else:
             wavs, n_samples = griffin_lim.griffin_lim_batch(mel, n_frames, hparams)
-    model.train(was_training)
     return inputs, mel, n_frames, wavs, n_samples
 
 
@@ -244,7 +233,6 @@ def copy_synthesis_scores(model, batch, hparams, vocoder=None, n_coeffs=13):
           audio  the waveform, analysed again with `mel_spectrogram_batch` and `pitch_batch`, against the recorded mel and the raw
                  frames_pitch: every key.
         An utterance whose synthesis has 0 frames scores NaN at both levels; it is not dropped. '''
-    from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
     inputs, mel, n_frames, wavs, n_samples = copy_synthesis(model, batch, hparams, vocoder)
     frames_pitch, mel_specs, output_lengths = inputs[7], inputs[8], inputs[9]
     longest = max(mel_specs.shape[2], mel.shape[2])

@@ -21,7 +21,7 @@ import torch
 
 from daft_exprt import _hip as H
 from daft_exprt import audio, evaluate, griffin_lim
-from daft_exprt.extract_features import mel_spectrogram_batch, pitch_batch
+from daft_exprt.recordings import _parameters_of, waves_to_device
 from daft_exprt.text import phonemize_sentence, prepare_sentences_for_inference  # noqa: F401
 from daft_exprt.vocoder import pcm16
 
@@ -145,7 +145,7 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
     inference = model.inference if hasattr(model, 'inference') else model.module.inference   # DDP-wrapped callers (270-278)
     targets = None
     if prosody_targets is not None:
-        from daft_exprt.clone import ProsodyTargets
+        from daft_exprt.clone import ProsodyTargets     # (`clone` imports this module for `_symbol_ids`)
         assert len(prosody_targets) == len(batch_sentences), f'{len(prosody_targets)} prosody targets for {len(batch_sentences)} sentences'
         targets = ProsodyTargets.stack(list(prosody_targets), int(col[4][0]), gpu)
     if targets is None:
@@ -186,30 +186,10 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
     return predictions
 
 
-def _parameters_of(wavs, lengths, hparams):
-    ''' [(energy (T,), pitch (T,), mel_spec (n_mel, T)) NumPy] of the (B, S) fp32 device waveforms `wavs` at
-        hparams.sampling_rate, zeros past their `lengths` (host ints): one `pitch_batch` and one `mel_spectrogram_batch` '''
-    n = torch.tensor(lengths, dtype=torch.int64, device=wavs.device)
-    pitch, n_pitch = pitch_batch(wavs, n, hparams)
-    mel, energy, n_mel = mel_spectrogram_batch(wavs, n, hparams)
-    pitch, energy, mel, n_pitch, n_mel = (t.cpu().numpy() for t in (pitch, energy, mel, n_pitch, n_mel))
-    out = []
-    for i in range(len(lengths)):
-        t = int(n_mel[i])
-        assert int(n_pitch[i]) == t, f'{int(n_pitch[i])} -- {t}'            # `generate.py:459`
-        out.append((energy[i, :t].copy(), pitch[i, :t].copy(), mel[i, :, :t].copy()))
-    return out
-
-
 def reference_parameters(audio_refs, hparams, device=None):
-    ''' [(energy, pitch, mel_spec)] of wav files, in order.  Files are read on the host (`audio.read_wav`), brought to
-        hparams.sampling_rate on the device (`audio.device_waves`: one launch per source rate), then tracked and analysed there
-        as one batch. '''
-    utts = []
-    for path in audio_refs:
-        y, rate = audio.read_wav(path)
-        utts.append(SimpleNamespace(samples=audio.to_float_mono(y), rate=rate))
-    wavs, lengths = audio.device_waves(utts, int(hparams.sampling_rate), H.device(device))
+    ''' [(energy, pitch, mel_spec)] of wav files, in order: read on the host and brought to hparams.sampling_rate on the device
+        (`recordings.waves_to_device`), then tracked and analysed there as one batch (`recordings._parameters_of`) '''
+    wavs, lengths = waves_to_device([SimpleNamespace(wav_file=path) for path in audio_refs], int(hparams.sampling_rate), H.device(device))
     return _parameters_of(wavs, lengths, hparams)
 
 
