@@ -993,6 +993,53 @@ int dx_ctc_loss(const float* logits, const int64_t* n_steps, const int64_t* labe
                 int* status, float* grad, float* ws, int B, int T, int U, int V, void* stream);
 int dx_ctc_greedy(const float* logits, const int64_t* n_steps, int* ids, int* n_out, float* score, int B, int T, int V, void* stream);
 
+/* ---- K31: a CTC phone recogniser trained on the corpus's own feature files, to score the intelligibility of a synthesis -- the CTC
+ * loss at utterance length with its gradient, greedy decoding, and the edit distance of the decode to the phones that were asked for
+ * (daft_exprt/recognizer.py; the reference has no counterpart).  Additive entry points (the ABI version stays).
+ *
+ * dx_uctc_loss / dx_uctc_greedy: arguments, outputs, status codes and mathematics are EXACTLY those of dx_ctc_loss / dx_ctc_greedy in
+ * the K30 comment above (z, lp, states, skip, lse3, alpha, log p, beta, c, gamma, post, grad, status; best, ids, score), with the same
+ * guarantees: words are independent; nothing at or past n_steps[b] / n_labels[b] is read; EVERY output element is written; a row gives
+ * the same bits alone, in any batch, with any padded extent T / U / B and whatever the outputs and the workspace held before; no
+ * atomics, two runs are bit-equal; all arithmetic is fp32.  What differs:
+ *   limits    T <= dx_uctc_max_steps() = 2048, U <= dx_uctc_max_labels() = 255 (S = 2 U + 1 <= 511), V <= dx_uctc_max_classes() = 128,
+ *             B <= 65535; beyond any of them DX_ERR_UNSUPPORTED before any launch
+ *   post      the blank's lane sum has four terms: lane i adds gamma(t, 2 i) + gamma(t, 2 (i + 64)) + gamma(t, 2 (i + 128)) +
+ *             gamma(t, 2 (i + 192)) in this order (a state at or past S counts 0), then the butterfly of dx_wave_sum.  For S <= 255
+ *             that is K30's sum; K31 is nevertheless only promised to agree with K30 within rounding, not bit for bit
+ *   ws        2 * B * T * (2 U + 1) floats of scratch: the alpha planes of all rows, then the beta planes.  Nothing in it has to be
+ *             initialised or to survive the call; the kernel reads back only cells it wrote in this call
+ *   layout    ONE WORKGROUP of four waves per row -- at ~1 000 steps the chain over t is the cost, not the number of rows.  (1) all
+ *             waves take the step log-sum-exps, four steps in flight per wave; (2) wave 0 runs the alpha chain forwards WHILE wave 1
+ *             runs the beta chain backwards (they are independent; K30 runs them in turn), K = 1, 2, 4 or 8 consecutive states per
+ *             lane (2 U + 1 <= 64 / 128 / 256 / 512), lane-edge neighbours one DPP move away, both planes to ws; (3) all waves turn
+ *             alpha + beta into the gradient, four steps per wave at a time, the scatter to classes being K30's gather over a per-row
+ *             list of label positions by class.  The greedy kernel: all waves take the arg-max and the step scores, one wave adds
+ *             the scores in order of t and collapses the path.
+ *
+ * dx_edit_distance: ref (B, R) / hyp (B, H) int32 with n_ref / n_hyp (B) int64 clamped into [0, R] / [0, H] (R = 0 or H = 0: the pointer
+ * may be NULL) -> counts (B, 4) int32 = substitutions, deletions, insertions, matches of one canonical cheapest alignment of
+ * ref[b, :n_ref[b]] with hyp[b, :n_hyp[b]].  Cell (i, j) aligns the first i reference entries with the first j of the hypothesis:
+ *   (i, 0) is i deletions, (0, j) is j insertions; otherwise the cheapest, at unit costs, of
+ *     diagonal   (i - 1, j - 1) -> (i, j): a match when ref[i - 1] == hyp[j - 1], else a substitution (a match costs 0)
+ *     deletion   (i - 1, j) -> (i, j)
+ *     insertion  (i, j - 1) -> (i, j)
+ *   among equal costs the diagonal wins, then the deletion, then the insertion.  The counts ride along with the cell, so there is no
+ *   back-trace: a cell stores its substitutions and deletions, and i and j give the rest (matches = i - sub - del, insertions =
+ *   j - i + del, cost = sub + del + insertions); counts[b] is cell (n_ref, n_hyp).
+ * All-integer, every element written, nothing at or past the lengths read, rows independent of their batch.  One workgroup per pair walks
+ * the anti-diagonals with three of them in LDS (as dx_dtw_align does).  R or H > dx_edit_max_len() = 2048 or B > 65535 returns
+ * DX_ERR_UNSUPPORTED before any launch. */
+long dx_uctc_max_steps(void);
+long dx_uctc_max_labels(void);
+long dx_uctc_max_classes(void);
+long dx_edit_max_len(void);
+int dx_uctc_loss(const float* logits, const int64_t* n_steps, const int64_t* labels, const int64_t* n_labels, const float* w, float* loss,
+                 int* status, float* grad, float* ws, int B, int T, int U, int V, void* stream);
+int dx_uctc_greedy(const float* logits, const int64_t* n_steps, int* ids, int* n_out, float* score, int B, int T, int V, void* stream);
+int dx_edit_distance(const int* ref, const int64_t* n_ref, const int* hyp, const int64_t* n_hyp, int* counts, int B, int R, int H,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Copy-synthesis scores of a checkpoint against held-out recordings of the same text:
     python scripts/evaluate.py -chk CHECKPOINT -vf FILE_LIST -out OUT_DIR [-bs 50] [-voc G_CKPT [-vcfg JSON]] [-n MAX_UTTERANCES] [-nc 13]
+                               [-rec RECOGNIZER]
 
   -chk  training checkpoint: weights, hyper-parameters and speaker statistics, as for `scripts/synthesize.py`
   -vf   a `features_dir|feature_file|speaker_id` list, e.g. the validation list `scripts/pre_process.py` writes; read through
@@ -9,6 +10,11 @@
         waveform instead of the Griffin-Lim preview
   -n    score the first N utterances of the list only
   -nc   cepstral coefficients 1..K of the distortion (default 13)
+  -rec  a phone recogniser (`scripts/train_recognizer.py`): every file also gets `per`, the phone error rate of the recogniser's
+        decode against the file's own phones at three levels -- `recording` (the recorded mel: the recogniser's own floor on that
+        utterance), `mel` (the decoder's mel) and `audio` (the re-analysed waveform) -- each with sub, del, ins, n_ref, per and n_hyp;
+        the summaries get per level the statistics of those keys and `rate`, the summed errors over the summed reference length.
+        Without -rec the report is what it always was.  How the rate tracks listeners has not been measured
 
 Every utterance is synthesised free-running -- predicted durations, predicted prosody, decoder -- with its own recording as the
 prosody reference and its own speaker, and compared with that recording after dynamic time warping (`daft_exprt/evaluate.py`,
@@ -41,25 +47,31 @@ def parse_args(argv=None):
     parser.add_argument('-vcfg', '--vocoder_config', default=None, help='HiFi-GAN config.json (default: beside the vocoder checkpoint)')
     parser.add_argument('-n', '--max_utterances', type=int, default=None, help='score the first N utterances of the list only')
     parser.add_argument('-nc', '--n_coeffs', type=int, default=13, help='cepstral coefficients 1..K of the distortion')
+    parser.add_argument('-rec', '--recognizer', default=None, help='phone recogniser (scripts/train_recognizer.py): add phone error rates')
     return parser.parse_args(argv)
 
 
-def score_files(model, hparams, list_file, batch_size, vocoder=None, max_utterances=None, n_coeffs=13):
-    ''' {file: {'speaker_id': id, 'mel': {key: value}, 'audio': {key: value}}} in the list's order; floats may be NaN '''
+def score_files(model, hparams, list_file, batch_size, vocoder=None, max_utterances=None, n_coeffs=13, recognizer=None):
+    ''' {file: {'speaker_id': id, 'mel': {key: value}, 'audio': {key: value}}} in the list's order; floats may be NaN.  With a
+        recogniser every file also has 'per': {level: {key: value}} for `evaluate.PER_LEVELS` and `recognizer.PER_KEYS` '''
     from daft_exprt.data_loader import DaftExprtDataCollate, DaftExprtDataLoader
-    from daft_exprt.evaluate import COPY_LEVELS, DTW_KEYS, copy_synthesis_scores
+    from daft_exprt.evaluate import COPY_LEVELS, DTW_KEYS, PER_LEVELS, copy_synthesis_scores
+    from daft_exprt.recognizer import PER_KEYS, per_to_host
     dataset = DaftExprtDataLoader(list_file, hparams, shuffle=False)
     collate = DaftExprtDataCollate(hparams)
     count = len(dataset) if max_utterances is None else min(len(dataset), max(0, max_utterances))
     records = {}
     for start in range(0, count, batch_size):
         batch = collate([dataset[i] for i in range(start, min(count, start + batch_size))])
-        scores = copy_synthesis_scores(model, batch, hparams, vocoder=vocoder, n_coeffs=n_coeffs)
+        scores = copy_synthesis_scores(model, batch, hparams, vocoder=vocoder, n_coeffs=n_coeffs, recognizer=recognizer)
         host = {level: {key: scores[level][key].cpu().tolist() for key in DTW_KEYS} for level in COPY_LEVELS}
+        per = {level: per_to_host(scores['per'][level]) for level in PER_LEVELS} if recognizer is not None else None
         for row, (features_dir, feature_file) in enumerate(zip(batch[11], batch[12])):
             name = f'{os.path.basename(os.path.normpath(features_dir))}/{feature_file}'
             records[name] = {'speaker_id': int(batch[10][row]),
                              **{level: {key: host[level][key][row] for key in DTW_KEYS} for level in COPY_LEVELS}}
+            if per is not None:
+                records[name]['per'] = {level: {key: per[level][key][row] for key in PER_KEYS} for level in PER_LEVELS}
     order = {f'{os.path.basename(os.path.normpath(line[0]))}/{line[1]}': i for i, line in enumerate(dataset.data)}
     return dict(sorted(records.items(), key=lambda item: order[item[0]]))
 
@@ -73,7 +85,15 @@ def _stats(values):
 def summarise(records, levels, keys):
     ''' per level and key the mean, median and count of the finite values: over all files, and per speaker '''
     def table(entries):
-        return {level: {key: _stats([e[level][key] for e in entries]) for key in keys} for level in levels}
+        out = {level: {key: _stats([e[level][key] for e in entries]) for key in keys} for level in levels}
+        if entries and 'per' in entries[0]:     # (-rec) per level the statistics of every key, and the corpus-level rate
+            out['per'] = {}
+            for level in entries[0]['per']:
+                rows = [e['per'][level] for e in entries]
+                n_ref = sum(r['n_ref'] for r in rows)
+                out['per'][level] = {**{key: _stats([r[key] for r in rows]) for key in rows[0]},
+                                     'rate': sum(r['sub'] + r['del'] + r['ins'] for r in rows) / n_ref if n_ref else None}
+        return out
     summary = {'files': len(records), **table(list(records.values())), 'speakers': {}}
     for speaker in sorted({e['speaker_id'] for e in records.values()}):
         mine = [e for e in records.values() if e['speaker_id'] == speaker]
@@ -87,6 +107,9 @@ def write_report(output_dir, records, audio, levels, keys):
         return None if isinstance(v, float) and not math.isfinite(v) else v
     files = {name: {'speaker_id': e['speaker_id'], **{level: {k: clean(v) for k, v in e[level].items()} for level in levels}}
              for name, e in records.items()}
+    for name, e in records.items():
+        if 'per' in e:
+            files[name]['per'] = {level: {k: clean(v) for k, v in values.items()} for level, values in e['per'].items()}
     report = {'audio': audio, 'files': files, 'summary': summarise(files, levels, keys)}
     os.makedirs(output_dir, exist_ok=True)
     path = os.path.join(output_dir, 'copy_synthesis.json')
@@ -99,6 +122,8 @@ def write_report(output_dir, records, audio, levels, keys):
                 _logger.info(f'{level} {key}: mean {s["mean"]:.3f}, median {s["median"]:.3f} over {s["count"]} of {len(files)} files')
             else:
                 _logger.info(f'{level} {key}: undefined for all {len(files)} files')
+    for level, s in report['summary'].get('per', {}).items():
+        _logger.info(f'{level} phone error rate: {s["rate"]} over {len(files)} files')
     _logger.info(f'Copy-synthesis scores written to {path}')
     return report
 
@@ -106,7 +131,8 @@ def write_report(output_dir, records, audio, levels, keys):
 def main(argv=None):
     args = parse_args(argv)
     logging.basicConfig(format='%(asctime)s [%(levelname)s] %(message)s', datefmt='%Y-%m-%d %H:%M:%S', level=logging.INFO)
-    for what, path in (('checkpoint', args.checkpoint), ('file list', args.validation_files), ('vocoder checkpoint', args.vocoder)):
+    for what, path in (('checkpoint', args.checkpoint), ('file list', args.validation_files), ('vocoder checkpoint', args.vocoder),
+                       ('recogniser', args.recognizer)):
         if path is not None and not os.path.isfile(path):
             raise SystemExit(f'evaluate.py: no such {what}: {path}')
     if args.batch_size < 1:
@@ -117,7 +143,11 @@ def main(argv=None):
     from daft_exprt.evaluate import COPY_LEVELS, DTW_KEYS
     model, hparams = load_model(args.checkpoint)
     vocoder = load_vocoder(args.vocoder, args.vocoder_config, hparams) if args.vocoder else None
-    records = score_files(model, hparams, args.validation_files, args.batch_size, vocoder, args.max_utterances, args.n_coeffs)
+    recognizer = None
+    if args.recognizer is not None:
+        from daft_exprt.recognizer import load_recognizer
+        recognizer = load_recognizer(args.recognizer)
+    records = score_files(model, hparams, args.validation_files, args.batch_size, vocoder, args.max_utterances, args.n_coeffs, recognizer)
     write_report(args.output_dir, records, 'hifi-gan' if vocoder is not None else 'griffin-lim', COPY_LEVELS, DTW_KEYS)
 
 

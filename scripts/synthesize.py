@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Batched prosody-transfer synthesis with objective scores, behind the flags of the reference's `scripts/synthesize.py`:
     python scripts/synthesize.py -out OUT_DIR -chk CHECKPOINT -tf SENTENCES -sb STYLE_BANK [-bs N] [-rtf] [-ctrl] [-voc G_CKPT [-vcfg JSON]]
-                                 [-dict DICTIONARY [-g2p G2P_CKPT]]
+                                 [-dict DICTIONARY [-g2p G2P_CKPT]] [-rec RECOGNIZER]
 
   -tf   phonemised sentences, one `file_name|{P1 P2} {P3} , {P4} ? ~` per line: the `sentences_to_generate.txt` the reference
         writes after text cleaning and g2p (`generate.read_phonemised_sentences`); with -dict: raw text, one sentence per line
@@ -16,6 +16,10 @@
         `fine_tuning_dataset`); -vcfg its `config.json` (default: the one beside the checkpoint).  The `.wav` files are then the
         vocoder's audio (16-bit PCM) instead of the Griffin-Lim preview, the scores refer to that audio, and -rtf logs a second
         real-time factor that includes the vocoder
+  -rec  a phone recogniser (`scripts/train_recognizer.py`): `<out>/intelligibility.json` then holds, per output file, the
+        substitutions, deletions and insertions of the recogniser's decode of the synthesised audio against the phones that were
+        asked for, their sum over the reference length (`per`), and the corpus-level rate (summed errors / summed reference
+        length).  How that rate tracks listeners has not been measured
 
 Every sentence gets a random reference of the style bank and a random speaker (`random.seed(1234)`), is synthesised with
 Griffin-Lim preview audio and scored on the device against its reference: `<out>/prosody_transfer.json` holds, per output file,
@@ -96,7 +100,7 @@ def phonemise(args, hparams):
     args.text_file = os.path.join(args.output_dir, 'sentences_to_generate.txt')
 
 
-def run(args, model, hparams, control=None, audio=True, scores=None, vocoder=None):
+def run(args, model, hparams, control=None, audio=True, scores=None, vocoder=None, recognizer=None, intelligibility=None):
     ''' one pass over the sentence file; returns [(sentence index, output name, reference .npz)] in sentence order.  With a
         vocoder the audio is its own; `audio` then only decides whether the pass is timed '''
     sentences, names = generate.read_phonemised_sentences(args.text_file, hparams.symbols)
@@ -111,7 +115,7 @@ def run(args, model, hparams, control=None, audio=True, scores=None, vocoder=Non
     predictions = generate.generate_mel_specs(model, sentences, list(names), speakers, refs, args.output_dir, hparams, dur_factors=dur,
                                               pitch_factors=pitch, batch_size=args.batch_size,
                                               use_griffin_lim=audio and vocoder is None, get_time_perf=not audio, scores=scores,
-                                              vocoder=vocoder)
+                                              vocoder=vocoder, recognizer=recognizer, intelligibility=intelligibility)
     outputs = []
     for idx, name in enumerate(names):      # the driver returns its own names, a batch at a time in order of length
         mine = [key for key in predictions if key.startswith(f'{name}_spk_{speakers[idx]}_ref_')]
@@ -169,6 +173,26 @@ def write_scores(args, scores, wav_names, audio='griffin-lim'):
     return report
 
 
+def write_intelligibility(args, intelligibility, wav_names, audio='griffin-lim'):
+    ''' `<out>/intelligibility.json`: {'audio': which audio was decoded, 'files': {name: sub, del, ins, n_ref, per, n_hyp + 'wav'},
+        'summary': the summed counts and 'rate' = summed errors / summed reference length (null without a reference phone)} '''
+    entries = {}
+    for name, values in intelligibility.items():
+        entry = {k: (None if isinstance(v, float) and math.isnan(v) else v) for k, v in values.items()}
+        entry['wav'] = f'{wav_names.get(name, name)}.wav'
+        entries[name] = entry
+    totals = {key: sum(e[key] for e in entries.values()) for key in ('sub', 'del', 'ins', 'n_ref', 'n_hyp')}
+    errors = totals['sub'] + totals['del'] + totals['ins']
+    report = {'audio': audio, 'files': entries,
+              'summary': {'files': len(entries), **totals, 'rate': errors / totals['n_ref'] if totals['n_ref'] else None}}
+    path = os.path.join(args.output_dir, 'intelligibility.json')
+    with open(path, 'w', encoding='utf-8') as f:
+        json.dump(report, f, indent=1)
+    _logger.info(f'phone error rate {report["summary"]["rate"]} ({errors} errors over {totals["n_ref"]} phones of {len(entries)} files); '
+                 f'written to {path}')
+    return report
+
+
 def main():
     parser = argparse.ArgumentParser(description='Synthesise phonemised sentences with prosody transferred from a style bank, and score the transfer')
     parser.add_argument('-out', '--output_dir', required=True, help='where the .npz, .wav and prosody_transfer.json go')
@@ -182,6 +206,7 @@ def main():
     parser.add_argument('-vcfg', '--vocoder_config', default=None, help='HiFi-GAN config.json (default: beside the vocoder checkpoint)')
     parser.add_argument('-dict', '--dictionary', default=None, help='pronunciation dictionary: -tf is then raw text and is phonemised first')
     parser.add_argument('-g2p', '--g2p', default=None, help='g2p model (scripts/train_g2p.py) for the words the dictionary lacks; needs -dict')
+    parser.add_argument('-rec', '--recognizer', default=None, help='phone recogniser (scripts/train_recognizer.py): write intelligibility.json')
     args = parser.parse_args()
     if args.g2p is not None and args.dictionary is None:
         parser.error('-g2p needs -dict')
@@ -197,10 +222,18 @@ def main():
         if vocoder is not None:
             run(args, model, hparams, audio=False, vocoder=vocoder)
             _logger.info(f'DaftExprt + HiFi-GAN RTF: {generate.LAST_TIME_PERF["rtf"]:.2f}')
-    scores = {}
-    outputs = run(args, model, hparams, control=CONTROL if args.control else None, scores=scores, vocoder=vocoder)
-    write_scores(args, scores, {} if args.control else pair_with_references(args, outputs),
-                 audio='hifi-gan' if vocoder is not None else 'griffin-lim')
+    recognizer = None
+    if args.recognizer is not None:
+        from daft_exprt.recognizer import load_recognizer
+        recognizer = load_recognizer(args.recognizer)
+    scores, intelligibility = {}, {}
+    outputs = run(args, model, hparams, control=CONTROL if args.control else None, scores=scores, vocoder=vocoder,
+                  recognizer=recognizer, intelligibility=intelligibility)
+    wav_names = {} if args.control else pair_with_references(args, outputs)
+    which = 'hifi-gan' if vocoder is not None else 'griffin-lim'
+    write_scores(args, scores, wav_names, audio=which)
+    if recognizer is not None:
+        write_intelligibility(args, intelligibility, wav_names, audio=which)
 
 
 if __name__ == '__main__':

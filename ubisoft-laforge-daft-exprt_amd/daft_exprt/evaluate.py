@@ -91,6 +91,7 @@ def prosody_transfer_scores(wavs, n_samples, pitch_refs, energy_refs, ref_length
 
 DTW_KEYS = ('mcd_db', 'f0_rmse_cents', 'vuv_error', 'voiced_pairs', 'path_len', 'frames_ref', 'frames_gen')
 COPY_LEVELS = ('mel', 'audio')
+PER_LEVELS = ('recording', 'mel', 'audio')      # scores['per'] of `copy_synthesis_scores(recognizer=...)`
 DTW_WORKSPACE_BYTES = 256 << 20         # default cap of the direction workspace: 256 pairs of 1000 x 1000 frames take 64 MB
 _DTW_WORKSPACE = {}                     # device -> grow-only byte tensor, kept across calls
 
@@ -225,14 +226,18 @@ def copy_synthesis(model, batch, hparams, vocoder=None):
     return inputs, mel, n_frames, wavs, n_samples
 
 
-def copy_synthesis_scores(model, batch, hparams, vocoder=None, n_coeffs=13):
+def copy_synthesis_scores(model, batch, hparams, vocoder=None, n_coeffs=13, recognizer=None, fold=None):
     ''' one collated data-loader batch (the 13-tuple `DaftExprtDataCollate` returns, `parse_batch`'s input) -> how close the
         free-running synthesis of each utterance (`copy_synthesis`) gets to its own recording.  Returns {'mel': scores,
         'audio': scores}, each {key: (B,) device tensor} for DTW_KEYS, rows in the batch's order:
           mel    the decoder's mel against the recorded mel: MCD and the frame counts (no audio, no pitch: those keys are NaN / 0)
           audio  the waveform, analysed again with `mel_spectrogram_batch` and `pitch_batch`, against the recorded mel and the raw
                  frames_pitch: every key.
-        An utterance whose synthesis has 0 frames scores NaN at both levels; it is not dropped. '''
+        An utterance whose synthesis has 0 frames scores NaN at both levels; it is not dropped.
+        `recognizer` (a `recognizer.Recognizer`; with None nothing is launched and nothing returned that was not before) adds
+        scores['per']: the phone error rates of `recognizer.phone_error_rates` (its keys, `fold` passed on) against the batch's own
+        symbols at the levels PER_LEVELS: `recording` -- the recorded mel, the recogniser's own floor on that utterance --, `mel`
+        -- the decoder's mel -- and `audio` -- the re-analysed waveform the DTW scores use. '''
     inputs, mel, n_frames, wavs, n_samples = copy_synthesis(model, batch, hparams, vocoder)
     frames_pitch, mel_specs, output_lengths = inputs[7], inputs[8], inputs[9]
     longest = max(mel_specs.shape[2], mel.shape[2])
@@ -257,4 +262,9 @@ def copy_synthesis_scores(model, batch, hparams, vocoder=None, n_coeffs=13):
             mel_audio[rows], pitch[rows, :sub_pitch.shape[1]] = sub_mel.float(), sub_pitch.float()
             n_audio[rows] = torch.minimum(sub_n_mel.long(), sub_n_pitch.long())
         scores['audio'] = dtw_scores_batch(mel_specs, output_lengths, mel_audio, n_audio, frames_pitch, pitch, n_coeffs=n_coeffs)
+        if recognizer is not None:
+            from daft_exprt.recognizer import phone_error_rates
+            symbols, input_lengths = inputs[0], inputs[5]
+            scores['per'] = {level: phone_error_rates(recognizer, m, n, symbols, input_lengths, fold)
+                             for level, m, n in zip(PER_LEVELS, (mel_specs, mel, mel_audio), (output_lengths, n_frames, n_audio))}
     return scores

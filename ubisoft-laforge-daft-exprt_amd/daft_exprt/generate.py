@@ -103,7 +103,8 @@ def _ref_name(ref, idx):
 
 def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_factors, batch_energy_factors, batch_pitch_factors,
                              pitch_transform, batch_speaker_ids, batch_file_names, output_dir, hparams, n_jobs=1,
-                             use_griffin_lim=True, scores=None, vocoder=None, prosody_targets=None):
+                             use_griffin_lim=True, scores=None, vocoder=None, prosody_targets=None, recognizer=None,
+                             intelligibility=None):
     ''' `generate.py:242-317`, same contract: every file name gets the `_spk_<id>_ref_<reference>` suffix IN PLACE
         (the caller's list is updated like the reference does, 248-253), one `model.inference` call on the collated
         batch, `<output_dir>/<file_name>.npz` holding `mel_spec` (298), and the return value
@@ -122,10 +123,16 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         audio.  With None nothing changes.
         `prosody_targets` (an extension): per sentence, in the caller's order, None or a one-row `clone.ProsodyTargets`
         of that sentence's symbols: per-symbol durations (frames), energies and pitches imposed on the predictions; raw units are
-        standardised with the sentence's speaker.  The collate's sort is applied to them.  With None nothing changes. '''
+        standardised with the sentence's speaker.  The collate's sort is applied to them.  With None nothing changes.
+        `recognizer` (an extension; needs `use_griffin_lim` or `vocoder`): a `recognizer.Recognizer`.  The dict
+        `intelligibility` then receives, per file name, the phone error rate of the generated audio against the phones that were
+        asked for (`recognizer.audio_error_rates`, on the device beside the audio): sub, del, ins, n_ref, per (NaN without a
+        reference phone) and n_hyp.  With None nothing is computed and nothing else changes. '''
     source = 'vocoder' if vocoder is not None else 'griffin_lim' if use_griffin_lim else None
     if scores is not None and source is None:
         raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
+    if recognizer is not None and (source is None or intelligibility is None):
+        raise ValueError('a recogniser scores generated audio into `intelligibility`: pass that dict, and use_griffin_lim=True or a vocoder')
     for idx, file_name in enumerate(batch_file_names):
         file_name += f'_spk_{batch_speaker_ids[idx]}'
         file_name += f'_ref_{_ref_name(batch_refs[idx], idx)}'
@@ -164,6 +171,9 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
     if source is not None:
         if scores is not None:
             batch_scores = evaluate.prosody_transfer_scores(wavs, n_samples, inputs[6], inputs[5], inputs[8], hparams)
+        if recognizer is not None:
+            from daft_exprt.recognizer import PER_KEYS, audio_error_rates, per_to_host
+            batch_per = audio_error_rates(recognizer, wavs, n_samples, inputs[0], inputs[4], hparams)
     duration, duration_int, energy, pitch, input_lengths = (t.detach().cpu().numpy() for t in encoder_preds)
     mel_spec, output_lengths = (t.detach().cpu().numpy() for t in decoder_preds)
     weights = alignments.detach().cpu().numpy()
@@ -182,6 +192,10 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
             host = {key: t.cpu().tolist() for key, t in batch_scores.items()}
             for i, name in enumerate(file_names):
                 scores[name] = {key: host[key][i] for key in evaluate.SCORE_KEYS}
+        if recognizer is not None:
+            host = per_to_host(batch_per)
+            for i, name in enumerate(file_names):
+                intelligibility[name] = {key: host[key][i] for key in PER_KEYS}
         _logger.warning('Mel-spec / alignment plots are outside the accelerated path')
     return predictions
 
@@ -264,13 +278,14 @@ LAST_TIME_PERF = {}   # filled by generate_mel_specs(get_time_perf=True): what t
 
 def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_dir, hparams, dur_factors=None,
                        energy_factors=None, pitch_factors=None, batch_size=1, n_jobs=1, use_griffin_lim=False,
-                       get_time_perf=False, scores=None, vocoder=None, prosody_targets=None):
+                       get_time_perf=False, scores=None, vocoder=None, prosody_targets=None, recognizer=None, intelligibility=None):
     ''' `generate.py:320-437`, same contract: `pitch_factors = [transform, [per-sentence factor lists]]`, the list-length
         asserts, eval mode + no grad, chunks of `batch_size`, returns the predictions dict only.  With `get_time_perf`
         the real-time factor is logged exactly like the reference: wall time of the whole per-batch function (collate,
         H2D, inference, D2H, file writes) against `((n_frames - 1) * hop + n_fft - 2 * (n_fft // 2)) / sr` seconds of
         audio per sentence (413-435); the numbers are also left in `LAST_TIME_PERF`.  `scores`, `vocoder`,
-        `prosody_targets` (one entry per sentence, in the caller's order): see `generate_batch_mel_specs`. '''
+        `prosody_targets` (one entry per sentence, in the caller's order), `recognizer` and `intelligibility`: see
+        `generate_batch_mel_specs`. '''
     if scores is not None and not use_griffin_lim and vocoder is None:
         raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
     n = len(sentences)
@@ -296,8 +311,10 @@ def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_d
             b_sent, b_refs, b_dur, b_en, b_pi, b_spk, b_names, b_targets = chunk
             begin = time.time() if get_time_perf else None
             extra = () if prosody_targets is None else (b_targets,)         # (without targets the call is the one it always was)
+            more = {} if recognizer is None else {'recognizer': recognizer, 'intelligibility': intelligibility}
             predictions.update(generate_batch_mel_specs(model, b_sent, b_refs, b_dur, b_en, b_pi, pitch_transform, b_spk,
-                                                        b_names, output_dir, hparams, n_jobs, use_griffin_lim, scores, vocoder, *extra))
+                                                        b_names, output_dir, hparams, n_jobs, use_griffin_lim, scores, vocoder, *extra,
+                                                        **more))
             time_per_batch += [time.time() - begin] if get_time_perf else []
     if get_time_perf:
         durations = []
