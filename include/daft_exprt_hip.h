@@ -1040,6 +1040,55 @@ int dx_uctc_greedy(const float* logits, const int64_t* n_steps, int* ids, int* n
 int dx_edit_distance(const int* ref, const int64_t* n_ref, const int* hyp, const int64_t* n_hyp, int* counts, int B, int R, int H,
                      void* stream);
 
+/* ---- K32: a speaker encoder trained on the corpus's own feature files, to score WHOSE voice a synthesis has -- attentive statistics
+ * pooling over the live steps of an utterance with its backward, and the score histograms of all verification trials of a set
+ * (daft_exprt/speaker.py; the reference has no counterpart).  Additive entry points (the ABI version stays).
+ *
+ * dx_attn_stat_pool_fwd: h (B, T, C) fp32 time-major, a (B, T) fp32 attention logits, n_steps (B) int64 -> out (B, 2 C) fp32 and
+ * stat (B, 2) fp32.  Per row b with n = clamp(n_steps[b], 0, T):
+ *   m      = max_{t < n} a[t]                      l = sum_{t < n} exp(a[t] - m)                 stat[b] = (m, l)
+ *   w[t]   = exp(a[t] - m) / l                     (the softmax of a over the live steps)
+ *   mu[c]  = sum_{t < n} w[t] h[t, c]
+ *   var[c] = sum_{t < n} w[t] (h[t, c] - mu[c])^2  -- about the mean, in a second pass over the row; never sum w h^2 - mu^2
+ *   sd[c]  = sqrt(var[c] + 1e-5)                   out[b] = [mu, sd]
+ *   n = 0: out[b] = 0 and stat[b] = (0, 0).
+ * dx_attn_stat_pool_bwd: the same h, a, n_steps, the out and stat of the forward and g_out (B, 2 C) = [g_mu, g_sd] -> g_h (B, T, C),
+ * g_a (B, T), with d[t, c] = h[t, c] - mu[c]:
+ *   g_h[t, c] = w[t] (g_mu[c] + g_sd[c] d[t, c] / sd[c])
+ *   q[t]      = sum_c (g_mu[c] d[t, c] + g_sd[c] d[t, c]^2 / (2 sd[c]))      (the g_mu term centred: sum_t w[t] d[t, c] = 0)
+ *   g_a[t]    = w[t] (q[t] - sum_{s < n} w[s] q[s])
+ *   +0 at and past n, and everywhere in a row with n = 0.
+ *   ws: B * ceil(C / 64) * T floats of scratch (the partial q of every 64-channel block); nothing in it has to be initialised.
+ * Guarantees of both: nothing of h or a at or past n is read; EVERY element of every output is written; all arithmetic is fp32; no
+ * atomics, two runs are bit-equal; a row gives the same bits alone, in any batch and with any padded extent T / B.
+ *   layout    one workgroup of four waves per (row, 64-channel block): the lanes along C (64 lanes x 4 B are one 256-B segment of a
+ *             step), the waves split t and combine through LDS in the order of the waves; the softmax weights of the row live in LDS.
+ *             The backward's q needs all channels: every block writes its partial q to ws and a second launch (one workgroup per
+ *             row) adds the blocks in order and forms g_a.
+ *   limits    1 <= C <= dx_spk_pool_max_channels() = 1024, 1 <= T <= dx_spk_pool_max_steps() = 4096, 1 <= B <= 65535; beyond them
+ *             DX_ERR_SHAPE / DX_ERR_UNSUPPORTED before any launch; a NULL pointer returns DX_ERR_ARG.
+ *
+ * dx_trial_counts: E (N, D) fp32, rows of unit length (not normalised here), spk (N) int32 -> counts (2, 4096) int64, zeroed by the
+ * entry point.  For every unordered pair i < j:
+ *   s   = sum_d E[i, d] E[j, d]                    (fp32, the exact-fp32 MFMA v_mfma_f32_32x32x2f32, d ascending in two interleaved
+ *                                                  halves of every 16)
+ *   bin = clamp(floor((s + 1) * 2048), 0, 4095)    (a NaN score counts in bin 0)
+ *   counts[spk[i] == spk[j] ? 0 : 1][bin] += 1     -- row 0 the target trials, row 1 the non-target trials
+ *   layout    the upper triangle of the N x N scores in 128 x 128 tiles, i < j masked on the diagonal tiles; a fixed number of
+ *             persistent workgroups loop over the tiles, count into two LDS histograms and flush their nonzero bins ONCE with
+ *             64-bit INTEGER global atomics -- order-independent, so two runs are bit-equal.
+ *   limits    1 <= D <= dx_trial_max_dim() = 1024 (any D: the tail of the last 16 is zero-filled), 1 <= N <= dx_trial_max_rows() =
+ *             65536; beyond them DX_ERR_SHAPE / DX_ERR_UNSUPPORTED before any launch; a NULL pointer returns DX_ERR_ARG. */
+long dx_spk_pool_max_channels(void);
+long dx_spk_pool_max_steps(void);
+long dx_trial_max_dim(void);
+long dx_trial_max_rows(void);
+int dx_attn_stat_pool_fwd(const float* h, const float* a, const int64_t* n_steps, float* out, float* stat, int B, int T, int C,
+                          void* stream);
+int dx_attn_stat_pool_bwd(const float* h, const float* a, const int64_t* n_steps, const float* out, const float* stat,
+                          const float* g_out, float* g_h, float* g_a, float* ws, int B, int T, int C, void* stream);
+int dx_trial_counts(const float* E, const int* spk, int64_t* counts, int N, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

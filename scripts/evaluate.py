@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Copy-synthesis scores of a checkpoint against held-out recordings of the same text:
     python scripts/evaluate.py -chk CHECKPOINT -vf FILE_LIST -out OUT_DIR [-bs 50] [-voc G_CKPT [-vcfg JSON]] [-n MAX_UTTERANCES] [-nc 13]
-                               [-rec RECOGNIZER]
+                               [-rec RECOGNIZER] [-spk SPEAKER_ENCODER]
 
   -chk  training checkpoint: weights, hyper-parameters and speaker statistics, as for `scripts/synthesize.py`
   -vf   a `features_dir|feature_file|speaker_id` list, e.g. the validation list `scripts/pre_process.py` writes; read through
@@ -15,6 +15,12 @@
         utterance), `mel` (the decoder's mel) and `audio` (the re-analysed waveform) -- each with sub, del, ins, n_ref, per and n_hyp;
         the summaries get per level the statistics of those keys and `rate`, the summed errors over the summed reference length.
         Without -rec the report is what it always was.  How the rate tracks listeners has not been measured
+  -spk  a speaker encoder (`scripts/train_speaker_encoder.py`): every file also gets `speaker`, at the same three levels --
+        `recording`, `mel`, `audio`; read them together -- the cosine of its embedding to the centroid of the file's own speaker
+        (`cos_target`), that cosine minus the largest to any other centroid (`margin`), whether the nearest centroid is the file's
+        speaker (`identified`) and whether cos_target reaches the encoder's threshold (`accepted`); the summaries get per level the
+        statistics of the two cosines and the shares identified and accepted.  Without -spk the report is what it always was.
+        How the cosines track listeners' judgement of speaker similarity has not been measured
 
 Every utterance is synthesised free-running -- predicted durations, predicted prosody, decoder -- with its own recording as the
 prosody reference and its own speaker, and compared with that recording after dynamic time warping (`daft_exprt/evaluate.py`,
@@ -48,30 +54,38 @@ def parse_args(argv=None):
     parser.add_argument('-n', '--max_utterances', type=int, default=None, help='score the first N utterances of the list only')
     parser.add_argument('-nc', '--n_coeffs', type=int, default=13, help='cepstral coefficients 1..K of the distortion')
     parser.add_argument('-rec', '--recognizer', default=None, help='phone recogniser (scripts/train_recognizer.py): add phone error rates')
+    parser.add_argument('-spk', '--speaker_encoder', default=None, help='speaker encoder (scripts/train_speaker_encoder.py): add speaker scores')
     return parser.parse_args(argv)
 
 
-def score_files(model, hparams, list_file, batch_size, vocoder=None, max_utterances=None, n_coeffs=13, recognizer=None):
+def score_files(model, hparams, list_file, batch_size, vocoder=None, max_utterances=None, n_coeffs=13, recognizer=None,
+                speaker_encoder=None):
     ''' {file: {'speaker_id': id, 'mel': {key: value}, 'audio': {key: value}}} in the list's order; floats may be NaN.  With a
-        recogniser every file also has 'per': {level: {key: value}} for `evaluate.PER_LEVELS` and `recognizer.PER_KEYS` '''
+        recogniser every file also has 'per': {level: {key: value}} for `evaluate.PER_LEVELS` and `recognizer.PER_KEYS`; with a
+        speaker encoder 'speaker': {level: {key: value}} for `evaluate.SPEAKER_LEVELS` and `speaker.SPEAKER_KEYS` '''
     from daft_exprt.data_loader import DaftExprtDataCollate, DaftExprtDataLoader
-    from daft_exprt.evaluate import COPY_LEVELS, DTW_KEYS, PER_LEVELS, copy_synthesis_scores
+    from daft_exprt.evaluate import COPY_LEVELS, DTW_KEYS, PER_LEVELS, SPEAKER_LEVELS, copy_synthesis_scores
     from daft_exprt.recognizer import PER_KEYS, per_to_host
+    from daft_exprt.speaker import SPEAKER_KEYS, scores_to_host
+    more = {} if speaker_encoder is None else {'speaker_encoder': speaker_encoder}     # (without one the call is the one it always was)
     dataset = DaftExprtDataLoader(list_file, hparams, shuffle=False)
     collate = DaftExprtDataCollate(hparams)
     count = len(dataset) if max_utterances is None else min(len(dataset), max(0, max_utterances))
     records = {}
     for start in range(0, count, batch_size):
         batch = collate([dataset[i] for i in range(start, min(count, start + batch_size))])
-        scores = copy_synthesis_scores(model, batch, hparams, vocoder=vocoder, n_coeffs=n_coeffs, recognizer=recognizer)
+        scores = copy_synthesis_scores(model, batch, hparams, vocoder=vocoder, n_coeffs=n_coeffs, recognizer=recognizer, **more)
         host = {level: {key: scores[level][key].cpu().tolist() for key in DTW_KEYS} for level in COPY_LEVELS}
         per = {level: per_to_host(scores['per'][level]) for level in PER_LEVELS} if recognizer is not None else None
+        spk = {level: scores_to_host(scores['speaker'][level]) for level in SPEAKER_LEVELS} if speaker_encoder is not None else None
         for row, (features_dir, feature_file) in enumerate(zip(batch[11], batch[12])):
             name = f'{os.path.basename(os.path.normpath(features_dir))}/{feature_file}'
             records[name] = {'speaker_id': int(batch[10][row]),
                              **{level: {key: host[level][key][row] for key in DTW_KEYS} for level in COPY_LEVELS}}
             if per is not None:
                 records[name]['per'] = {level: {key: per[level][key][row] for key in PER_KEYS} for level in PER_LEVELS}
+            if spk is not None:
+                records[name]['speaker'] = {level: {key: spk[level][key][row] for key in SPEAKER_KEYS} for level in SPEAKER_LEVELS}
     order = {f'{os.path.basename(os.path.normpath(line[0]))}/{line[1]}': i for i, line in enumerate(dataset.data)}
     return dict(sorted(records.items(), key=lambda item: order[item[0]]))
 
@@ -93,6 +107,12 @@ def summarise(records, levels, keys):
                 n_ref = sum(r['n_ref'] for r in rows)
                 out['per'][level] = {**{key: _stats([r[key] for r in rows]) for key in rows[0]},
                                      'rate': sum(r['sub'] + r['del'] + r['ins'] for r in rows) / n_ref if n_ref else None}
+        if entries and 'speaker' in entries[0]:  # (-spk) per level the statistics of the cosines and the shares identified / accepted
+            out['speaker'] = {}
+            for level in entries[0]['speaker']:
+                rows = [e['speaker'][level] for e in entries]
+                out['speaker'][level] = {key: sum(bool(r[key]) for r in rows) / len(rows) if key in ('identified', 'accepted')
+                                         else _stats([r[key] for r in rows]) for key in rows[0]}
         return out
     summary = {'files': len(records), **table(list(records.values())), 'speakers': {}}
     for speaker in sorted({e['speaker_id'] for e in records.values()}):
@@ -110,6 +130,8 @@ def write_report(output_dir, records, audio, levels, keys):
     for name, e in records.items():
         if 'per' in e:
             files[name]['per'] = {level: {k: clean(v) for k, v in values.items()} for level, values in e['per'].items()}
+        if 'speaker' in e:
+            files[name]['speaker'] = {level: {k: clean(v) for k, v in values.items()} for level, values in e['speaker'].items()}
     report = {'audio': audio, 'files': files, 'summary': summarise(files, levels, keys)}
     os.makedirs(output_dir, exist_ok=True)
     path = os.path.join(output_dir, 'copy_synthesis.json')
@@ -124,6 +146,9 @@ def write_report(output_dir, records, audio, levels, keys):
                 _logger.info(f'{level} {key}: undefined for all {len(files)} files')
     for level, s in report['summary'].get('per', {}).items():
         _logger.info(f'{level} phone error rate: {s["rate"]} over {len(files)} files')
+    for level, s in report['summary'].get('speaker', {}).items():
+        _logger.info(f'{level} speaker: identified {s["identified"]:.3f}, accepted {s["accepted"]:.3f}, mean cosine to the own centroid '
+                     f'{s["cos_target"]["mean"]} over {len(files)} files')
     _logger.info(f'Copy-synthesis scores written to {path}')
     return report
 
@@ -132,7 +157,7 @@ def main(argv=None):
     args = parse_args(argv)
     logging.basicConfig(format='%(asctime)s [%(levelname)s] %(message)s', datefmt='%Y-%m-%d %H:%M:%S', level=logging.INFO)
     for what, path in (('checkpoint', args.checkpoint), ('file list', args.validation_files), ('vocoder checkpoint', args.vocoder),
-                       ('recogniser', args.recognizer)):
+                       ('recogniser', args.recognizer), ('speaker encoder', args.speaker_encoder)):
         if path is not None and not os.path.isfile(path):
             raise SystemExit(f'evaluate.py: no such {what}: {path}')
     if args.batch_size < 1:
@@ -147,7 +172,12 @@ def main(argv=None):
     if args.recognizer is not None:
         from daft_exprt.recognizer import load_recognizer
         recognizer = load_recognizer(args.recognizer)
-    records = score_files(model, hparams, args.validation_files, args.batch_size, vocoder, args.max_utterances, args.n_coeffs, recognizer)
+    speaker_encoder = None
+    if args.speaker_encoder is not None:
+        from daft_exprt.speaker import load_speaker_encoder
+        speaker_encoder = load_speaker_encoder(args.speaker_encoder)
+    records = score_files(model, hparams, args.validation_files, args.batch_size, vocoder, args.max_utterances, args.n_coeffs, recognizer,
+                          speaker_encoder)
     write_report(args.output_dir, records, 'hifi-gan' if vocoder is not None else 'griffin-lim', COPY_LEVELS, DTW_KEYS)
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Batched prosody-transfer synthesis with objective scores, behind the flags of the reference's `scripts/synthesize.py`:
     python scripts/synthesize.py -out OUT_DIR -chk CHECKPOINT -tf SENTENCES -sb STYLE_BANK [-bs N] [-rtf] [-ctrl] [-voc G_CKPT [-vcfg JSON]]
-                                 [-dict DICTIONARY [-g2p G2P_CKPT]] [-rec RECOGNIZER]
+                                 [-dict DICTIONARY [-g2p G2P_CKPT]] [-rec RECOGNIZER] [-spk SPEAKER_ENCODER]
 
   -tf   phonemised sentences, one `file_name|{P1 P2} {P3} , {P4} ? ~` per line: the `sentences_to_generate.txt` the reference
         writes after text cleaning and g2p (`generate.read_phonemised_sentences`); with -dict: raw text, one sentence per line
@@ -20,6 +20,14 @@
         substitutions, deletions and insertions of the recogniser's decode of the synthesised audio against the phones that were
         asked for, their sum over the reference length (`per`), and the corpus-level rate (summed errors / summed reference
         length).  How that rate tracks listeners has not been measured
+  -spk  a speaker encoder (`scripts/train_speaker_encoder.py`): `<out>/speaker_identity.json` then holds, per output file, the
+        requested speaker, the reference, the speaker whose centroid the reference RECORDING is nearest to
+        (`reference_identified_as`), and of the synthesised audio the cosine to the requested speaker's centroid (`cos_target`),
+        its `margin` over the other centroids, whether it is `identified` as and `accepted` for the requested speaker, and the
+        cosine to the embedding of the reference recording (`cos_reference`).  The summary has the share identified and, over the
+        files whose reference is nearest to another speaker, the mean of cos_target - cos_reference and the share where it is
+        negative: the leak of the reference's speaker that the model's adversarial speaker classifier exists to prevent.  How the
+        cosines track listeners' judgement of speaker similarity has not been measured
 
 Every sentence gets a random reference of the style bank and a random speaker (`random.seed(1234)`), is synthesised with
 Griffin-Lim preview audio and scored on the device against its reference: `<out>/prosody_transfer.json` holds, per output file,
@@ -100,7 +108,8 @@ def phonemise(args, hparams):
     args.text_file = os.path.join(args.output_dir, 'sentences_to_generate.txt')
 
 
-def run(args, model, hparams, control=None, audio=True, scores=None, vocoder=None, recognizer=None, intelligibility=None):
+def run(args, model, hparams, control=None, audio=True, scores=None, vocoder=None, recognizer=None, intelligibility=None,
+        speaker_encoder=None, speaker_identity=None):
     ''' one pass over the sentence file; returns [(sentence index, output name, reference .npz)] in sentence order.  With a
         vocoder the audio is its own; `audio` then only decides whether the pass is timed '''
     sentences, names = generate.read_phonemised_sentences(args.text_file, hparams.symbols)
@@ -112,10 +121,11 @@ def run(args, model, hparams, control=None, audio=True, scores=None, vocoder=Non
         dur = [[control['duration']] * n_symbols(s) for s in sentences]
         pitch = [control['pitch_transform'], [[control['pitch']] * n_symbols(s) for s in sentences]]
     os.makedirs(args.output_dir, exist_ok=True)
+    more = {} if speaker_encoder is None else {'speaker_encoder': speaker_encoder, 'speaker_identity': speaker_identity}
     predictions = generate.generate_mel_specs(model, sentences, list(names), speakers, refs, args.output_dir, hparams, dur_factors=dur,
                                               pitch_factors=pitch, batch_size=args.batch_size,
                                               use_griffin_lim=audio and vocoder is None, get_time_perf=not audio, scores=scores,
-                                              vocoder=vocoder, recognizer=recognizer, intelligibility=intelligibility)
+                                              vocoder=vocoder, recognizer=recognizer, intelligibility=intelligibility, **more)
     outputs = []
     for idx, name in enumerate(names):      # the driver returns its own names, a batch at a time in order of length
         mine = [key for key in predictions if key.startswith(f'{name}_spk_{speakers[idx]}_ref_')]
@@ -193,6 +203,35 @@ def write_intelligibility(args, intelligibility, wav_names, audio='griffin-lim')
     return report
 
 
+def write_speaker_identity(args, speaker_identity, wav_names, audio='griffin-lim'):
+    ''' `<out>/speaker_identity.json`: {'audio': which audio was embedded, 'files': {name: speaker_id, reference,
+        reference_identified_as, cos_target, margin, identified, accepted, cos_reference + 'wav'}, 'summary': files, the shares
+        `identified` as and `accepted` for the requested speaker, and over the `other_reference` files whose reference recording is
+        nearest to ANOTHER speaker's centroid: `target_minus_reference`, the mean of cos_target - cos_reference, and `leaked`, the
+        share where it is negative -- the synthesis is closer to the reference's voice than to the requested one (both null
+        without such a file)} '''
+    entries = {}
+    for name, values in speaker_identity.items():
+        entry = {k: (None if isinstance(v, float) and math.isnan(v) else v) for k, v in values.items()}
+        entry['wav'] = f'{wav_names.get(name, name)}.wav'
+        entries[name] = entry
+    other = [e['cos_target'] - e['cos_reference'] for e in entries.values()
+             if e['reference_identified_as'] != e['speaker_id'] and e['cos_target'] is not None and e['cos_reference'] is not None]
+    summary = {'files': len(entries),
+               'identified': sum(e['identified'] for e in entries.values()) / len(entries) if entries else None,
+               'accepted': sum(e['accepted'] for e in entries.values()) / len(entries) if entries else None,
+               'other_reference': len(other), 'target_minus_reference': statistics.fmean(other) if other else None,
+               'leaked': sum(d < 0 for d in other) / len(other) if other else None}
+    report = {'audio': audio, 'files': entries, 'summary': summary}
+    path = os.path.join(args.output_dir, 'speaker_identity.json')
+    with open(path, 'w', encoding='utf-8') as f:
+        json.dump(report, f, indent=1)
+    _logger.info(f'identified as the requested speaker: {summary["identified"]} of {len(entries)} files; with a reference of another '
+                 f'speaker ({len(other)} files): cos_target - cos_reference {summary["target_minus_reference"]}, leaked '
+                 f'{summary["leaked"]}; written to {path}')
+    return report
+
+
 def main():
     parser = argparse.ArgumentParser(description='Synthesise phonemised sentences with prosody transferred from a style bank, and score the transfer')
     parser.add_argument('-out', '--output_dir', required=True, help='where the .npz, .wav and prosody_transfer.json go')
@@ -207,6 +246,8 @@ def main():
     parser.add_argument('-dict', '--dictionary', default=None, help='pronunciation dictionary: -tf is then raw text and is phonemised first')
     parser.add_argument('-g2p', '--g2p', default=None, help='g2p model (scripts/train_g2p.py) for the words the dictionary lacks; needs -dict')
     parser.add_argument('-rec', '--recognizer', default=None, help='phone recogniser (scripts/train_recognizer.py): write intelligibility.json')
+    parser.add_argument('-spk', '--speaker_encoder', default=None,
+                        help='speaker encoder (scripts/train_speaker_encoder.py): write speaker_identity.json')
     args = parser.parse_args()
     if args.g2p is not None and args.dictionary is None:
         parser.error('-g2p needs -dict')
@@ -226,14 +267,21 @@ def main():
     if args.recognizer is not None:
         from daft_exprt.recognizer import load_recognizer
         recognizer = load_recognizer(args.recognizer)
-    scores, intelligibility = {}, {}
+    speaker_encoder = None
+    if args.speaker_encoder is not None:
+        from daft_exprt.speaker import load_speaker_encoder
+        speaker_encoder = load_speaker_encoder(args.speaker_encoder)
+    scores, intelligibility, speaker_identity = {}, {}, {}
     outputs = run(args, model, hparams, control=CONTROL if args.control else None, scores=scores, vocoder=vocoder,
-                  recognizer=recognizer, intelligibility=intelligibility)
+                  recognizer=recognizer, intelligibility=intelligibility, speaker_encoder=speaker_encoder,
+                  speaker_identity=speaker_identity)
     wav_names = {} if args.control else pair_with_references(args, outputs)
     which = 'hifi-gan' if vocoder is not None else 'griffin-lim'
     write_scores(args, scores, wav_names, audio=which)
     if recognizer is not None:
         write_intelligibility(args, intelligibility, wav_names, audio=which)
+    if speaker_encoder is not None:
+        write_speaker_identity(args, speaker_identity, wav_names, audio=which)
 
 
 if __name__ == '__main__':

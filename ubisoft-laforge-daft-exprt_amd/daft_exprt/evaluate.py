@@ -92,6 +92,7 @@ def prosody_transfer_scores(wavs, n_samples, pitch_refs, energy_refs, ref_length
 DTW_KEYS = ('mcd_db', 'f0_rmse_cents', 'vuv_error', 'voiced_pairs', 'path_len', 'frames_ref', 'frames_gen')
 COPY_LEVELS = ('mel', 'audio')
 PER_LEVELS = ('recording', 'mel', 'audio')      # scores['per'] of `copy_synthesis_scores(recognizer=...)`
+SPEAKER_LEVELS = PER_LEVELS                      # scores['speaker'] of `copy_synthesis_scores(speaker_encoder=...)`
 DTW_WORKSPACE_BYTES = 256 << 20         # default cap of the direction workspace: 256 pairs of 1000 x 1000 frames take 64 MB
 _DTW_WORKSPACE = {}                     # device -> grow-only byte tensor, kept across calls
 
@@ -226,7 +227,7 @@ def copy_synthesis(model, batch, hparams, vocoder=None):
     return inputs, mel, n_frames, wavs, n_samples
 
 
-def copy_synthesis_scores(model, batch, hparams, vocoder=None, n_coeffs=13, recognizer=None, fold=None):
+def copy_synthesis_scores(model, batch, hparams, vocoder=None, n_coeffs=13, recognizer=None, fold=None, speaker_encoder=None):
     ''' one collated data-loader batch (the 13-tuple `DaftExprtDataCollate` returns, `parse_batch`'s input) -> how close the
         free-running synthesis of each utterance (`copy_synthesis`) gets to its own recording.  Returns {'mel': scores,
         'audio': scores}, each {key: (B,) device tensor} for DTW_KEYS, rows in the batch's order:
@@ -237,7 +238,11 @@ def copy_synthesis_scores(model, batch, hparams, vocoder=None, n_coeffs=13, reco
         `recognizer` (a `recognizer.Recognizer`; with None nothing is launched and nothing returned that was not before) adds
         scores['per']: the phone error rates of `recognizer.phone_error_rates` (its keys, `fold` passed on) against the batch's own
         symbols at the levels PER_LEVELS: `recording` -- the recorded mel, the recogniser's own floor on that utterance --, `mel`
-        -- the decoder's mel -- and `audio` -- the re-analysed waveform the DTW scores use. '''
+        -- the decoder's mel -- and `audio` -- the re-analysed waveform the DTW scores use.
+        `speaker_encoder` (a `speaker.SpeakerEncoder` with centroids; with None nothing is launched and nothing returned that was
+        not before) adds scores['speaker']: `speaker.speaker_scores` (cos_target, margin, identified, accepted) against the batch's
+        own speaker ids at the same three levels, SPEAKER_LEVELS -- read them together: the recording's row is the encoder's own
+        floor on that utterance. '''
     inputs, mel, n_frames, wavs, n_samples = copy_synthesis(model, batch, hparams, vocoder)
     frames_pitch, mel_specs, output_lengths = inputs[7], inputs[8], inputs[9]
     longest = max(mel_specs.shape[2], mel.shape[2])
@@ -267,4 +272,8 @@ def copy_synthesis_scores(model, batch, hparams, vocoder=None, n_coeffs=13, reco
             symbols, input_lengths = inputs[0], inputs[5]
             scores['per'] = {level: phone_error_rates(recognizer, m, n, symbols, input_lengths, fold)
                              for level, m, n in zip(PER_LEVELS, (mel_specs, mel, mel_audio), (output_lengths, n_frames, n_audio))}
+        if speaker_encoder is not None:
+            from daft_exprt.speaker import speaker_scores
+            scores['speaker'] = {level: speaker_scores(speaker_encoder, m, n, batch[10])
+                                 for level, m, n in zip(SPEAKER_LEVELS, (mel_specs, mel, mel_audio), (output_lengths, n_frames, n_audio))}
     return scores

@@ -104,7 +104,7 @@ def _ref_name(ref, idx):
 def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_factors, batch_energy_factors, batch_pitch_factors,
                              pitch_transform, batch_speaker_ids, batch_file_names, output_dir, hparams, n_jobs=1,
                              use_griffin_lim=True, scores=None, vocoder=None, prosody_targets=None, recognizer=None,
-                             intelligibility=None):
+                             intelligibility=None, speaker_encoder=None, speaker_identity=None):
     ''' `generate.py:242-317`, same contract: every file name gets the `_spk_<id>_ref_<reference>` suffix IN PLACE
         (the caller's list is updated like the reference does, 248-253), one `model.inference` call on the collated
         batch, `<output_dir>/<file_name>.npz` holding `mel_spec` (298), and the return value
@@ -127,16 +127,26 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         `recognizer` (an extension; needs `use_griffin_lim` or `vocoder`): a `recognizer.Recognizer`.  The dict
         `intelligibility` then receives, per file name, the phone error rate of the generated audio against the phones that were
         asked for (`recognizer.audio_error_rates`, on the device beside the audio): sub, del, ins, n_ref, per (NaN without a
-        reference phone) and n_hyp.  With None nothing is computed and nothing else changes. '''
+        reference phone) and n_hyp.  With None nothing is computed and nothing else changes.
+        `speaker_encoder` (an extension; needs `use_griffin_lim` or `vocoder`): a `speaker.SpeakerEncoder` with centroids.
+        The dict `speaker_identity` then receives, per file name: `speaker_id` (the speaker that was asked for), `reference` (the
+        reference's name), `reference_identified_as` (the speaker whose centroid the REFERENCE recording's mel is nearest to), and
+        `speaker.audio_speaker_scores` of the generated audio against the requested speaker -- cos_target, margin, identified,
+        accepted -- with cos_reference, the cosine to the embedding of the reference recording itself.  With None nothing is
+        computed and nothing else changes. '''
     source = 'vocoder' if vocoder is not None else 'griffin_lim' if use_griffin_lim else None
     if scores is not None and source is None:
         raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
     if recognizer is not None and (source is None or intelligibility is None):
         raise ValueError('a recogniser scores generated audio into `intelligibility`: pass that dict, and use_griffin_lim=True or a vocoder')
+    if speaker_encoder is not None and (source is None or speaker_identity is None):
+        raise ValueError('a speaker encoder scores generated audio into `speaker_identity`: pass that dict, and use_griffin_lim=True or a vocoder')
+    reference_of = {}
     for idx, file_name in enumerate(batch_file_names):
         file_name += f'_spk_{batch_speaker_ids[idx]}'
         file_name += f'_ref_{_ref_name(batch_refs[idx], idx)}'
         batch_file_names[idx] = file_name
+        reference_of[file_name] = _ref_name(batch_refs[idx], idx)
         _logger.info(f'Generating "{batch_sentences[idx]}" as "{file_name}"')
     col = collate_tensors(batch_sentences, batch_dur_factors, batch_energy_factors, batch_pitch_factors, pitch_transform,
                           batch_refs, batch_speaker_ids, batch_file_names, hparams)
@@ -174,6 +184,12 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
         if recognizer is not None:
             from daft_exprt.recognizer import PER_KEYS, audio_error_rates, per_to_host
             batch_per = audio_error_rates(recognizer, wavs, n_samples, inputs[0], inputs[4], hparams)
+        if speaker_encoder is not None:
+            from daft_exprt.speaker import audio_speaker_scores, nearest_speakers, scores_to_host
+            with torch.no_grad():
+                reference_embeddings = speaker_encoder.embed(inputs[7].float(), inputs[8])
+            batch_spk = audio_speaker_scores(speaker_encoder, wavs, n_samples, inputs[9], hparams, reference_embeddings)
+            reference_speakers = nearest_speakers(speaker_encoder, reference_embeddings)
     duration, duration_int, energy, pitch, input_lengths = (t.detach().cpu().numpy() for t in encoder_preds)
     mel_spec, output_lengths = (t.detach().cpu().numpy() for t in decoder_preds)
     weights = alignments.detach().cpu().numpy()
@@ -196,6 +212,11 @@ def generate_batch_mel_specs(model, batch_sentences, batch_refs, batch_dur_facto
             host = per_to_host(batch_per)
             for i, name in enumerate(file_names):
                 intelligibility[name] = {key: host[key][i] for key in PER_KEYS}
+        if speaker_encoder is not None:
+            host, requested = scores_to_host(batch_spk), inputs[9].cpu().tolist()
+            for i, name in enumerate(file_names):
+                speaker_identity[name] = {'speaker_id': requested[i], 'reference': reference_of[name],
+                                          'reference_identified_as': reference_speakers[i], **{key: host[key][i] for key in host}}
         _logger.warning('Mel-spec / alignment plots are outside the accelerated path')
     return predictions
 
@@ -278,14 +299,15 @@ LAST_TIME_PERF = {}   # filled by generate_mel_specs(get_time_perf=True): what t
 
 def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_dir, hparams, dur_factors=None,
                        energy_factors=None, pitch_factors=None, batch_size=1, n_jobs=1, use_griffin_lim=False,
-                       get_time_perf=False, scores=None, vocoder=None, prosody_targets=None, recognizer=None, intelligibility=None):
+                       get_time_perf=False, scores=None, vocoder=None, prosody_targets=None, recognizer=None, intelligibility=None,
+                       speaker_encoder=None, speaker_identity=None):
     ''' `generate.py:320-437`, same contract: `pitch_factors = [transform, [per-sentence factor lists]]`, the list-length
         asserts, eval mode + no grad, chunks of `batch_size`, returns the predictions dict only.  With `get_time_perf`
         the real-time factor is logged exactly like the reference: wall time of the whole per-batch function (collate,
         H2D, inference, D2H, file writes) against `((n_frames - 1) * hop + n_fft - 2 * (n_fft // 2)) / sr` seconds of
         audio per sentence (413-435); the numbers are also left in `LAST_TIME_PERF`.  `scores`, `vocoder`,
-        `prosody_targets` (one entry per sentence, in the caller's order), `recognizer` and `intelligibility`: see
-        `generate_batch_mel_specs`. '''
+        `prosody_targets` (one entry per sentence, in the caller's order), `recognizer` and `intelligibility`, `speaker_encoder`
+        and `speaker_identity`: see `generate_batch_mel_specs`. '''
     if scores is not None and not use_griffin_lim and vocoder is None:
         raise ValueError('scores are computed from generated audio: pass use_griffin_lim=True (the Griffin-Lim preview) or a vocoder')
     n = len(sentences)
@@ -312,6 +334,8 @@ def generate_mel_specs(model, sentences, file_names, speaker_ids, refs, output_d
             begin = time.time() if get_time_perf else None
             extra = () if prosody_targets is None else (b_targets,)         # (without targets the call is the one it always was)
             more = {} if recognizer is None else {'recognizer': recognizer, 'intelligibility': intelligibility}
+            if speaker_encoder is not None:
+                more.update(speaker_encoder=speaker_encoder, speaker_identity=speaker_identity)
             predictions.update(generate_batch_mel_specs(model, b_sent, b_refs, b_dur, b_en, b_pi, pitch_transform, b_spk,
                                                         b_names, output_dir, hparams, n_jobs, use_griffin_lim, scores, vocoder, *extra,
                                                         **more))
