@@ -384,8 +384,11 @@ def test_planned_conv_ln_and_lnbwd_match_unplanned(film):
 
 
 @pytest.mark.parametrize('film', [False, True])
-@pytest.mark.parametrize('lens_list,N', [([700, 433, 257, 256, 130, 5], 700), ([1000, 999, 31, 1, 0, 640, 512, 300], 1000), ([40, 17], 40)])
-def test_splitk_conv_ln_and_lnbwd_match_ring_kernel_and_fp32_reference(film, lens_list, N):
+@pytest.mark.parametrize('lens_list,N,tiles', [pytest.param([700, 433, 257, 256, 130, 5], 700, None, id='lens_list0-700'),
+                                               pytest.param([1000, 999, 31, 1, 0, 640, 512, 300], 1000, None, id='lens_list1-1000'),
+                                               pytest.param([40, 17], 40, None, id='lens_list2-40'),
+                                               pytest.param([700, 433, 257], 700, 9, id='tall-700-tiles9')])
+def test_splitk_conv_ln_and_lnbwd_match_ring_kernel_and_fp32_reference(film, lens_list, N, tiles):
     ''' the split-K kernel (fragment-order weights from L2 into registers, the K slices of a workgroup added through LDS: four for a
         tile of up to 128 rows, two for 129..192 rows, taller tiles are two workgroups) on the balanced tiles of the ring kernel: same
         inputs, same dropout counters -> results equal up to the fp32 summation order of the contraction (2 or 4 partial sums instead
@@ -404,7 +407,8 @@ def test_splitk_conv_ln_and_lnbwd_match_ring_kernel_and_fp32_reference(film, len
     bias, gamma, beta = (torch.randn(128, generator=g).to(DEV) for _ in range(3))
     res = torch.randn(B, N, 128, generator=g).to(DEV) * valid
     fl = torch.randn(B, 256, generator=g).to(DEV) if film else None
-    plan = ops.conv_tile_plan(lens, N)
+    plan = ops.conv_tile_plan(lens, N, tiles=tiles)          # tiles = B * ceil(N / 256): 129..175-row tiles (KS = 2 and KS = 4, n0 > 0)
+    assert tiles is None or (plan[0].shape[0] == tiles == B * -(-N // 256) and int(plan[0][:, 2].max()) == 175)
     ring = ops.conv1d_ln(x, wp, bias, res, gamma, beta, lens, film=fl, save=True, p_pre=0.1, seed_pre=9, lp_copy=True, plan=plan)
     sk = ops.conv1d_ln(x, wp, bias, res, gamma, beta, lens, film=fl, save=True, p_pre=0.1, seed_pre=9, lp_copy=True, plan=plan, w_frag=wf)
     sk2 = ops.conv1d_ln(x, wp, bias, res, gamma, beta, lens, film=fl, save=True, p_pre=0.1, seed_pre=9, lp_copy=True, plan=plan, w_frag=wf)
