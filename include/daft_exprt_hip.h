@@ -1089,6 +1089,30 @@ int dx_attn_stat_pool_bwd(const float* h, const float* a, const int64_t* n_steps
                           const float* g_out, float* g_h, float* g_a, float* ws, int B, int T, int C, void* stream);
 int dx_trial_counts(const float* E, const int* spk, int64_t* counts, int N, int D, void* stream);
 
+/* ---- K33: weight gradients of the HiFi-GAN generator's convolutions (K24) -- what fine-tuning the vocoder adds; the forward and
+ * both data gradients are K24 launches with re-packed weights.  Additive entry points (the ABI version stays).  Layout and contract
+ * are K24's: x (B, N, Cin) and dy time-major fp32, rows ld* floats apart, n_rows (B) int64 = the live rows of x; rows < 0 or
+ * >= n_rows[b] of x and of dy count as zeros and are NEVER READ.  w_dtype = the operand type: DX_BF16 rounds dy and
+ * leaky_relu(x, in_slope) to bf16 when they are staged (v_mfma_f32_32x32x16_bf16), DX_F32 is exact (v_mfma_f32_32x32x2_f32);
+ * accumulation fp32.  in_slope = the slope the forward applied to x (1: none).
+ *
+ * dx_vocoder_wgrad: dy (B, N, Cout);  dw [tap][Cout][Cin] fp32, the forward's packed order:
+ *     dw[tap][co][ci] = sum_{b, t < n_rows[b]} dy[b, t, co] * leaky_relu(x[b, t + (tap - (taps - 1) / 2) * dilation, ci])
+ * dx_vocoder_upsample_wgrad: dy (B, N * u, Cout), read as (B, N, u * Cout);  dw [u][ceil(k / u)][Cout][Cin] fp32, the order of the
+ *     forward's w_packed: entry (p, s) contracts dy rows t u + p with x rows t + (p + pad) div u - s; entries whose tap
+ *     j = (p + pad) mod u + s u >= k are written as zeros.
+ * The contraction over the rows is split by the shapes alone (never by n_rows) over workgroups that write partial tiles to ws; a
+ * second launch adds them in index order into dw, every element of which is written.  No atomics: two calls give the same bits.
+ * ws: dx_vocoder_wgrad_workspace(B, N, Cin, Cout, k, u) bytes (u = 1 for dx_vocoder_wgrad, k = taps), 16-byte aligned; nothing in it has to
+ * be initialised.  x, dy, dw 16-byte aligned, ldx and lddy multiples of 4.
+ * Cin or Cout no multiple of 32, or (taps - 1) * dilation > 64: DX_ERR_UNSUPPORTED before any launch (conv_pre comes in with its
+ * input channels zero-padded to a multiple of 32, as in the forward). */
+long dx_vocoder_wgrad_workspace(int B, int N, int Cin, int Cout, int k, int u);
+int dx_vocoder_wgrad(const float* x, long ldx, const float* dy, long lddy, int w_dtype, float* dw, float* ws, const int64_t* n_rows,
+                 int B, int N, int Cin, int Cout, int taps, int dilation, float in_slope, void* stream);
+int dx_vocoder_upsample_wgrad(const float* x, long ldx, const float* dy, long lddy, int w_dtype, float* dw, float* ws,
+                          const int64_t* n_rows, int B, int N, int Cin, int Cout, int k, int u, float in_slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

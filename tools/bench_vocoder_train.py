@@ -1,0 +1,228 @@
+#!/usr/bin/env python
+"""One step of HiFi-GAN's own fine-tuning (V1 generator, batch 16, segment 8192, weights from a seed) on one MI355X through
+`daft_exprt/vocoder_train.py`, `fp32` and `bf16` operands.
+
+One JSON line: ms per training step (device events, median of --reps after a warm-up), the share of one instrumented step that
+goes to the generator's forward launches, its data-gradient launches, the gate / bias pointwise ops, `dx_vocoder_wgrad` with its reduce
+launch, the discriminators (forward + backward, with the backward of the losses and of conv_post: what is left of the backward pass),
+the losses and the optimisers (events around each piece: kernel time plus its launch gaps), `dx_vocoder_wgrad`'s TFLOP/s per input
+channel width -- and, as yardstick, the same generator's forward + backward through `F.conv1d` / `F.conv_transpose1d` autograd on
+the same device, weights and segment.  The yardstick lives here only: it is no path of the package.
+Run:  python tools/bench_vocoder_train.py [--reps 5] [--batch 16] [--segment 8192]
+"""
+import argparse
+import json
+import os
+import sys
+import warnings
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'ubisoft-laforge-daft-exprt_amd')):
+    sys.path.insert(0, p)
+
+
+def _events():
+    return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+
+def _timed(fn, reps):
+    ts = []
+    for _ in range(reps):
+        s, e = _events()
+        s.record()
+        fn()
+        e.record()
+        torch.cuda.synchronize()
+        ts.append(s.elapsed_time(e))
+    return float(np.median(ts))
+
+
+class Marks:
+    ''' device-event pairs per kind; `wrap` times every call of a function, `span` a block '''
+    def __init__(self):
+        self.marks, self.flop = [], {}
+
+    def wrap(self, fn, kind_of, flop_of=None):
+        def f(*a, **kw):
+            s, e = _events()
+            s.record()
+            out = fn(*a, **kw)
+            e.record()
+            kind = kind_of(*a, **kw)
+            self.marks.append((kind, s, e))
+            if flop_of is not None:
+                key, flop = flop_of(*a, **kw)
+                self.flop.setdefault(key, []).append((flop, s, e))
+            return out
+        return f
+
+    def span(self, kind):
+        marks = self.marks
+
+        class _Span:
+            def __enter__(self):
+                self.s, self.e = _events()
+                self.s.record()
+
+            def __exit__(self, *exc):
+                self.e.record()
+                marks.append((kind, self.s, self.e))
+        return _Span()
+
+    def totals(self):
+        out = {}
+        for kind, s, e in self.marks:
+            out[kind] = out.get(kind, 0.) + s.elapsed_time(e)
+        return out
+
+
+def torch_generator(cfg, weights, mel):
+    ''' the yardstick: HiFi-GAN's generator on torch's own convolutions, (B, C, T) layout, no sequence ends '''
+    nk = len(cfg['resblock_kernel_sizes'])
+    lrelu = lambda x, s=0.1: F.leaky_relu(x, s)      # noqa: E731
+    conv = lambda x, name, d: F.conv1d(x, *weights[name], dilation=d, padding=d * (weights[name][0].shape[2] - 1) // 2)      # noqa: E731
+    x = conv(mel, 'conv_pre', 1)
+    for i, (u, k) in enumerate(zip(cfg['upsample_rates'], cfg['upsample_kernel_sizes'])):
+        x = F.conv_transpose1d(lrelu(x), *weights[f'ups.{i}'], stride=u, padding=(k - u) // 2)
+        total = None
+        for j, dils in enumerate(cfg['resblock_dilation_sizes']):
+            r, name = x, f'resblocks.{i * nk + j}'
+            for m, d in enumerate(dils):
+                if str(cfg['resblock']) == '1':
+                    r = r + conv(lrelu(conv(lrelu(r), f'{name}.convs1.{m}', d)), f'{name}.convs2.{m}', 1)
+                else:
+                    r = r + conv(lrelu(r), f'{name}.convs.{m}', d)
+            total = r if total is None else total + r
+        x = total / nk
+    return torch.tanh(conv(lrelu(x, 0.01), 'conv_post', 1))[:, 0]
+
+
+def instrumented_step(VT, generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio):
+    ''' `vocoder_train.train_step` with events around its pieces; returns (share of the step per piece, wgrad TFLOP/s per width) '''
+    mk = Marks()
+    saved = {n: getattr(VT, n) for n in ('conv_forward', 'upsample_forward', 'conv_wgrad', 'upsample_wgrad', '_gate', '_bias_grad')}
+    VT.conv_forward = mk.wrap(saved['conv_forward'], lambda x, wp, bias, *a, **kw: 'generator_data_gradients' if bias is None else 'generator_forward')
+    VT.upsample_forward = mk.wrap(saved['upsample_forward'], lambda *a, **kw: 'generator_forward')
+    VT.conv_wgrad = mk.wrap(saved['conv_wgrad'], lambda *a, **kw: 'wgrad',
+                            lambda x, dy, n, k, *a, **kw: (x.shape[2], 2. * x.shape[0] * x.shape[1] * x.shape[2] * dy.shape[2] * k))
+    VT.upsample_wgrad = mk.wrap(saved['upsample_wgrad'], lambda *a, **kw: 'wgrad',
+                                lambda x, dy, n, k, *a, **kw: (x.shape[2], 2. * x.shape[0] * x.shape[1] * x.shape[2] * dy.shape[2] * k))
+    VT._gate = mk.wrap(saved['_gate'], lambda *a, **kw: 'gate_bias_pointwise')
+    VT._bias_grad = mk.wrap(saved['_bias_grad'], lambda *a, **kw: 'gate_bias_pointwise')
+    try:
+        B, _, frames = mel.shape
+        lengths = torch.full((B,), frames, dtype=torch.int64, device=mel.device)
+        y = audio[:, None]
+        whole_s, whole_e = _events()
+        whole_s.record()
+        with mk.span('generator_forward_all'):
+            y_hat = generator(mel, lengths)[:, None]
+        optim_d.zero_grad(set_to_none=True)
+        with mk.span('discriminators'):
+            loss_d = 0.
+            for disc in (mpd, msd):
+                real, fake, _, _ = disc(y, y_hat.detach())
+                loss_d = loss_d + VT.discriminator_loss(real, fake)
+            loss_d.backward()
+        with mk.span('optimisers'):
+            optim_d.step()
+        optim_g.zero_grad(set_to_none=True)
+        with mk.span('losses'):
+            l_mel = VT.mel_l1(loss_mel(audio), loss_mel(y_hat[:, 0]))
+        l_adv, l_fm = 0., 0.
+        with mk.span('discriminators'):
+            outs = [disc(y, y_hat) for disc in (mpd, msd)]
+        with mk.span('losses'):
+            for _, fake, fmap_r, fmap_g in outs:
+                l_adv = l_adv + VT.generator_adversarial_loss(fake)
+                l_fm = l_fm + VT.feature_matching_loss(fmap_r, fmap_g)
+            loss = l_adv + l_fm + VT.MEL_LOSS_WEIGHT * l_mel
+        with mk.span('backward_all'):
+            loss.backward()
+        with mk.span('optimisers'):
+            optim_g.step()
+        whole_e.record()
+        torch.cuda.synchronize()
+    finally:
+        for n, fn in saved.items():
+            setattr(VT, n, fn)
+    t = mk.totals()
+    whole = whole_s.elapsed_time(whole_e)
+    inside = sum(t.get(k, 0.) for k in ('generator_data_gradients', 'wgrad', 'gate_bias_pointwise'))
+    # the forward launches of the generator run inside generator_forward_all; what the backward pass holds beside the generator's
+    # launches is the discriminators' backward, the losses' and conv_post's
+    pieces = {'generator_forward': t.pop('generator_forward_all'), 'generator_data_gradients': t.get('generator_data_gradients', 0.),
+              'gate_bias_pointwise': t.get('gate_bias_pointwise', 0.), 'wgrad_with_reduce': t.get('wgrad', 0.),
+              'discriminators_forward_backward': t.get('discriminators', 0.) + t['backward_all'] - inside,
+              'losses': t.get('losses', 0.), 'optimisers': t.get('optimisers', 0.)}
+    share = {k: v / whole for k, v in pieces.items()}
+    share['unaccounted'] = 1. - sum(share.values())
+    rate = {str(width): sum(f for f, _, _ in calls) / (sum(s.elapsed_time(e) for _, s, e in calls) * 1e-3) / 1e12
+            for width, calls in sorted(mk.flop.items())}
+    return whole, share, rate
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--segment', type=int, default=8192)
+    args = ap.parse_args()
+    warnings.simplefilter('ignore')
+    from daft_exprt import vocoder_train as VT
+    from tests import vocoder_oracle as O
+    dev = torch.device('cuda:0')
+    cfg = dict(O.V1, n_fft=1024, win_size=1024, fmin=0, fmax=8000, fmax_for_loss=None)
+    frames = args.segment // cfg['hop_size']
+    seed_mel = O.make_mel(cfg, (12,), seed=0)
+    weights = O.make_weights(cfg, seed_mel, (12,), seed=0)
+    sd = O.state_dict(weights, 'weight_norm')
+    g = torch.Generator().manual_seed(1)
+    mel = (torch.randn((args.batch, cfg['num_mels'], frames), generator=g) * 1.5 - 4.).to(dev)
+    audio = (0.1 * torch.randn((args.batch, args.segment), generator=g)).to(dev)
+    proj = torch.randn((args.batch, args.segment), generator=g).to(dev)
+    lengths = torch.full((args.batch,), frames, dtype=torch.int64, device=dev)
+    out = {'metric': 'hifi_gan_fine_tuning_step', 'config': 'V1', 'batch': args.batch, 'segment': args.segment}
+    torch.manual_seed(0)
+    loss_mel = VT.LossMel(cfg).to(dev)
+    for dtype in ('fp32', 'bf16'):
+        generator = VT.TrainableGenerator(cfg, sd, compute_dtype=dtype).to(dev)
+        mpd, msd = VT.MultiPeriodDiscriminator().to(dev), VT.MultiScaleDiscriminator().to(dev)
+        optim_g = torch.optim.AdamW(generator.parameters(), VT.LEARNING_RATE, betas=VT.ADAM_BETAS)
+        optim_d = torch.optim.AdamW(list(msd.parameters()) + list(mpd.parameters()), VT.LEARNING_RATE, betas=VT.ADAM_BETAS)
+        step = lambda: VT.train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio)      # noqa: E731
+        for _ in range(2):                                                    # warm-up: code objects, workspaces, torch's conv choices
+            step()
+        torch.cuda.synchronize()
+        ms = _timed(step, args.reps)
+        whole, share, rate = instrumented_step(VT, generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio)
+
+        def gen_fwd_bwd():
+            for p in generator.parameters():
+                p.grad = None
+            (generator(mel, lengths) * proj).sum().backward()
+        gen_fwd_bwd()
+        torch.cuda.synchronize()
+        out[dtype] = {'ms_per_step': ms, 'instrumented_step_ms': whole, 'share': share, 'wgrad_tflops_by_cin': rate,
+                      'generator_forward_backward_ms': _timed(gen_fwd_bwd, args.reps)}
+        del generator, mpd, msd, optim_g, optim_d
+        torch.cuda.empty_cache()
+    tw = {name: (w.to(dev).requires_grad_(True), b.to(dev).requires_grad_(True)) for name, (w, b) in weights.items()}
+
+    def torch_fwd_bwd():
+        for w, b in tw.values():
+            w.grad = b.grad = None
+        (torch_generator(cfg, tw, mel) * proj).sum().backward()
+    for _ in range(2):
+        torch_fwd_bwd()
+    torch.cuda.synchronize()
+    out['torch_conv1d_generator_forward_backward_ms'] = _timed(torch_fwd_bwd, args.reps)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

@@ -143,6 +143,53 @@ def pack_upsample_weight(w, u, dtype):
     return p.to(dtype).contiguous()
 
 
+def upsample_tap_table(k, u):
+    ''' (tap j of entry (p, s) as a (u, ceil(k / u)) int64 tensor, -1 where j >= k; entry p * taps + s that holds tap j, (k,)) of
+        `pack_upsample_weight`'s order: every tap j < k sits in exactly one entry '''
+    pad, taps = (k - u) // 2, -(-k // u)
+    j = (torch.arange(u)[:, None] + pad) % u + torch.arange(taps)[None, :] * u
+    j = torch.where(j < k, j, torch.full_like(j, -1))
+    entry = torch.empty((k,), dtype=torch.int64)
+    live = j.flatten() >= 0
+    entry[j.flatten()[live]] = torch.arange(u * taps)[live]
+    return j, entry
+
+
+def pack_conv_dgrad_weight(w, dtype, cout_pad=None):
+    ''' Conv1d weight (Cout, Cin, k) -> [k][Cin (zero-padded to cout_pad)][Cout], taps reversed: `dx_voc_conv` over dy with this
+        weight, the same dilation, in_slope 1 and no bias is the convolution's data gradient.  Any device; differentiable. '''
+    cout, cin, k = w.shape
+    p = w.flip(2).permute(2, 1, 0)
+    if cout_pad is not None and cout_pad > cin:
+        p = torch.cat([p, p.new_zeros((k, cout_pad - cin, cout))], dim=1)
+    return p.to(dtype).contiguous()
+
+
+def upsample_dgrad_taps(k, u):
+    ''' taps of the stride-1 convolution that is ConvTranspose1d(k, stride u)'s data gradient over dy viewed as (B, N, u Cout):
+        the smallest odd span symmetric about 0 that holds every row offset s - (p + pad) div u (3 for k = 2 u, 5 for k 7 / u 3) '''
+    pad, taps = (k - u) // 2, -(-k // u)
+    return 2 * max(taps - 1, (u - 1 + pad) // u) + 1
+
+
+def pack_upsample_dgrad_weight(w, u, dtype):
+    ''' ConvTranspose1d weight (Cin, Cout, k) -> [taps'][Cin][u * Cout], taps' = `upsample_dgrad_taps(k, u)`: row offset
+        o = s - (p + pad) div u of column block p holds tap j = (p + pad) mod u + s u, zeros where there is none.  `dx_voc_conv` over
+        dy (B, N u, Cout) read as (B, N, u Cout) with this weight, dilation 1, in_slope 1 and no bias is the transposed convolution's
+        data gradient.  Any device; differentiable. '''
+    cin, cout, k = w.shape
+    pad, taps_d = (k - u) // 2, upsample_dgrad_taps(k, u)
+    half = taps_d // 2
+    o = torch.arange(taps_d)[:, None] - half                       # (taps', 1)
+    p = torch.arange(u)[None, :]                                   # (1, u)
+    s = o + (p + pad) // u
+    j = (p + pad) % u + s * u
+    live = (s >= 0) & (j < k)
+    j = torch.where(live, j, torch.zeros_like(j)).to(w.device)
+    g = w[:, :, j] * live.to(device=w.device, dtype=w.dtype)       # (Cin, Cout, taps', u)
+    return g.permute(2, 0, 3, 1).reshape(taps_d, cin, u * cout).to(dtype).contiguous()
+
+
 def pcm16(wavs):
     ''' [-1, 1] fp32 -> int16 as HiFi-GAN's inference writes it (x 32768, truncated toward zero), saturating instead of wrapping '''
     return (wavs * 32768.).clamp(-32768., 32767.).to(torch.int16)
