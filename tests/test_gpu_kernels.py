@@ -172,7 +172,7 @@ def test_layernorm_dropout_forward_backward_consistency(C):
     assert abs(zeros - 0.3) < 0.02, zeros
 
 
-def test_wgrad_matches_autograd_all_dtype_pairs():
+def test_wgrad_matches_autograd_all_dtype_pairs(monkeypatch):
     from daft_exprt import ops
     from oracle import daft_exprt_cpu as O
     g = torch.Generator().manual_seed(9)
@@ -187,14 +187,13 @@ def test_wgrad_matches_autograd_all_dtype_pairs():
         for cd, dyt, xt, tol in ((torch.float32, torch.float32, torch.float32, 2e-5), (torch.bfloat16, torch.bfloat16, torch.float32, 2e-2),
                                  (torch.bfloat16, torch.float32, torch.bfloat16, 2e-2), (torch.bfloat16, torch.bfloat16, torch.bfloat16, 2e-2)):
             for use_ws in (True, False):                      # partial tiles + fixed-order reduce | fp32 atomics
-                ops.WGRAD_WORKSPACE = use_ws
+                monkeypatch.setattr(ops, 'WGRAD_WORKSPACE', use_ws)          # (undone at teardown, whatever fails below)
                 dw = torch.zeros(Cout, Cin, taps, device=DEV) if taps == 3 else torch.zeros(Cout, Cin, device=DEV)
                 db = torch.zeros(Cout, device=DEV)
                 ops.conv1d_wgrad(dy.to(DEV).to(dyt), x.to(DEV).to(xt), dw, db, cd, lens.to(DEV))
                 ref = w.grad if taps == 3 else w.grad[:, :, 0]
                 assert float((dw.cpu() - ref).abs().max()) <= tol * float(ref.abs().max()), (taps, cd, dyt, xt, use_ws)
                 assert float((db.cpu() - b.grad).abs().max()) <= tol * float(b.grad.abs().max()) + 1e-4, (taps, cd, use_ws)
-            ops.WGRAD_WORKSPACE = True
         w.grad = None
 
 
