@@ -1113,6 +1113,34 @@ int dx_vocoder_wgrad(const float* x, long ldx, const float* dy, long lddy, int w
 int dx_vocoder_upsample_wgrad(const float* x, long ldx, const float* dy, long lddy, int w_dtype, float* dw, float* ws,
                           const int64_t* n_rows, int B, int N, int Cin, int Cout, int k, int u, float in_slope, void* stream);
 
+/* ---- K34: the anti-aliased periodic activation of the BigVGAN generator (Lee et al. 2023: `Activation1d` with ratio 2 and
+ * 12-tap filters around `Snake` / `SnakeBeta`), the one operation that generator adds to K24's.  Additive entry points (the ABI
+ * version stays).  Layout is K24's: x, y (B, N, C) time-major fp32, rows ld* floats apart, n_rows (B) int64.
+ *
+ * dx_vocoder_snake: per utterance b with n = n_rows[b] live rows and per channel c, clamp(i, lo, hi) clamping the index,
+ *     u[t] = 2 * sum_i f_up[t + 15 - 2 i] * x[clamp(i - 5, 0, n - 1)]       t in [0, 2 n), over the i with 0 <= t + 15 - 2 i < 12
+ *     s[t] = u[t] + inv_beta[c] * sin(alpha[c] * u[t])^2
+ *     y[m] = sum_{k < 12} f_down[k] * s[clamp(2 m + k - 5, 0, 2 n - 1)]     m in [0, n)
+ * i.e. replicate-pad (5, 5), transposed conv of stride 2, crop [15 : -15], the activation, replicate-pad (5, 6), conv of stride 2.
+ * The first clamp replicates the edge ROW of x, the second the edge VALUE of s (u is not continued past the edge).
+ *   alpha, inv_beta  (C) fp32 on the device, in their final form: the host applies exp() for `snake_logscale` and computes
+ *                    inv_beta = 1 / (beta + 1e-9) (beta = alpha for `snake`) in float64;
+ *   filters          a HOST pointer to 24 floats, f_up[12] then f_down[12]; they travel in the kernel's argument block.
+ * Sequence ends, K24's contract in its strict form: rows >= n_rows[b] of x are NEVER READ -- the edge row is replicated, the one place
+ * where a dead row is not a zero; rows >= n_rows[b] of y are written as zeros up to N; n_rows[b] = 0 writes zeros only.  No atomics,
+ * no LDS: u and s live in registers, every s is computed once per tile of dx_vocoder_snake_tile_rows() rows (plus 11 of halo), and
+ * an utterance gets the same bits alone, in any batch, at any N, whatever the buffers held.  fp32 throughout, the accurate sinf.
+ * y must not alias x.  x, y, alpha, inv_beta 16-byte aligned; C, ldx, ldy multiples of 4 (DX_ERR_UNSUPPORTED otherwise), more
+ * workgroups than grid.x holds likewise -- all before any launch.
+ *
+ * dx_vocoder_post_clamp: dx_voc_post (arguments, contract and kernel) with clamp(v, -1, 1) in place of tanh(v): what the
+ * generator ends in when its config says `use_tanh_at_final: false`. */
+int dx_vocoder_snake_tile_rows(void);
+int dx_vocoder_snake(const float* x, long ldx, const float* alpha, const float* inv_beta, const float* filters, float* y, long ldy,
+                     const int64_t* n_rows, int B, int N, int C, void* stream);
+int dx_vocoder_post_clamp(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, const int64_t* n_rows,
+                          int B, int N, int C, int taps, float in_slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,8 +56,8 @@ def parse_args(argv=None):
     parser.add_argument('--aligner', default=None, help='learned aligner checkpoint (default: align with the checkpoint itself)')
     parser.add_argument('--clone', type=_quantities, default=QUANTITIES, help='quantities to impose: dur,energy,pitch')
     parser.add_argument('--normalise', choices=('self', 'source', 'target'), default='self', help='statistics of the energy / pitch targets')
-    parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN generator checkpoint (default: Griffin-Lim preview)')
-    parser.add_argument('-vcfg', '--vocoder_config', default=None, help='HiFi-GAN config.json (default: beside the vocoder checkpoint)')
+    parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN or BigVGAN generator checkpoint (default: Griffin-Lim preview)')
+    parser.add_argument('-vcfg', '--vocoder_config', default=None, help='its config.json (default: beside the vocoder checkpoint)')
     parser.add_argument('-mf', '--min_frames', type=int, default=3, help='fewest frames of a sounding symbol')
     parser.add_argument('-trim', '--trim_db', type=float, default=-40.0, help='silence threshold below the peak frame energy, dB (<= 0)')
     return parser.parse_args(argv)

@@ -49,8 +49,8 @@ def parse_args(argv=None):
     parser.add_argument('-vf', '--validation_files', required=True, help='list of features_dir|feature_file|speaker_id lines')
     parser.add_argument('-out', '--output_dir', required=True, help='where copy_synthesis.json goes')
     parser.add_argument('-bs', '--batch_size', type=int, default=50, help='utterances per inference call')
-    parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN generator checkpoint: score its audio instead of the Griffin-Lim preview')
-    parser.add_argument('-vcfg', '--vocoder_config', default=None, help='HiFi-GAN config.json (default: beside the vocoder checkpoint)')
+    parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN or BigVGAN generator checkpoint: score its audio instead of the Griffin-Lim preview')
+    parser.add_argument('-vcfg', '--vocoder_config', default=None, help='its config.json (default: beside the vocoder checkpoint)')
     parser.add_argument('-n', '--max_utterances', type=int, default=None, help='score the first N utterances of the list only')
     parser.add_argument('-nc', '--n_coeffs', type=int, default=13, help='cepstral coefficients 1..K of the distortion')
     parser.add_argument('-rec', '--recognizer', default=None, help='phone recogniser (scripts/train_recognizer.py): add phone error rates')

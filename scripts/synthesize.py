@@ -241,8 +241,8 @@ def main():
     parser.add_argument('-bs', '--batch_size', type=int, default=50, help='sentences per inference call')
     parser.add_argument('-rtf', '--real_time_factor', action='store_true', help='first time a pass without audio and log its real-time factor')
     parser.add_argument('-ctrl', '--control', action='store_true', help='apply the duration x 1.25, pitch + 50 Hz example to every symbol')
-    parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN generator checkpoint: write and score its audio instead of the Griffin-Lim preview')
-    parser.add_argument('-vcfg', '--vocoder_config', default=None, help='HiFi-GAN config.json (default: beside the vocoder checkpoint)')
+    parser.add_argument('-voc', '--vocoder', default=None, help='HiFi-GAN or BigVGAN generator checkpoint: write and score its audio instead of the Griffin-Lim preview')
+    parser.add_argument('-vcfg', '--vocoder_config', default=None, help='its config.json (default: beside the vocoder checkpoint)')
     parser.add_argument('-dict', '--dictionary', default=None, help='pronunciation dictionary: -tf is then raw text and is phonemised first')
     parser.add_argument('-g2p', '--g2p', default=None, help='g2p model (scripts/train_g2p.py) for the words the dictionary lacks; needs -dict')
     parser.add_argument('-rec', '--recognizer', default=None, help='phone recogniser (scripts/train_recognizer.py): write intelligibility.json')

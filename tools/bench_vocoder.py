@@ -8,7 +8,11 @@ bytes the algorithm needs (computed from the shapes here: every activation read 
 device-event time of that kind's launches in one instrumented call (events around each launch: kernel time plus its launch gap),
 the share of the bound and which bound it is (MFMA / vector peak or HBM: 2.5 PFLOP/s bf16, 157.3 TFLOP/s fp32, 8 TB/s, MI355X
 spec); the Griffin-Lim preview of the same batch beside it.  Kernel times proper: run under `rocprofv3 --kernel-trace --stats`.
-Run:  python tools/bench_vocoder.py [--reps 5] [--batch 256]
+`--bigvgan` adds, under "bigvgan", the same measurement of a BigVGAN generator of the base layout (V1's shapes with `snakebeta`
+activations, weights from a seed) on the same batch, with one more kind: `snake`, the launches of the anti-aliased activation
+(`dx_vocoder_snake`), their bytes (every activation read and written once), their rate, that rate against the 6.29 TB/s a float4
+copy reaches on this chip, and their share of the call.
+Run:  python tools/bench_vocoder.py [--reps 5] [--batch 256] [--bigvgan]
 """
 import argparse
 import json
@@ -24,6 +28,7 @@ for p in (ROOT, os.path.join(ROOT, 'ubisoft-laforge-daft-exprt_amd')):
 
 PEAK = {'bf16': 2.5e15, 'fp32': 157.3e12}
 PEAK_HBM = 8.0e12
+COPY_RATE = 6.29e12          # a float4 copy on this chip (measured; the guide's figure)
 
 
 def _timed(fn, reps):
@@ -61,6 +66,19 @@ def layer_costs(cfg, frames, w_bytes):
     return costs
 
 
+def snake_cost(cfg, frames):
+    ''' [flop, min bytes] of every anti-aliased activation of a BigVGAN generator: per row and channel 24 + 24 multiply-adds of
+        the two 12-tap filters (2 x 6 taps per upsampled sample, two of them per row; 12 per output) -- the two sinf are not counted
+        -- and the activation read and written once as fp32 '''
+    rows, c, flop, byts = frames, cfg['upsample_initial_channel'], 0., 0.
+    per_block = sum(len(d) for d in cfg['resblock_dilation_sizes']) * (2 if str(cfg['resblock']) == '1' else 1)
+    for i, u in enumerate(cfg['upsample_rates']):
+        rows, c = rows * u, c // 2
+        launches = per_block + (1 if i == len(cfg['upsample_rates']) - 1 else 0)               # + activation_post
+        flop, byts = flop + launches * 2. * 36 * rows * c, byts + launches * 8. * rows * c
+    return [flop, byts]
+
+
 def per_kind_ms(voc, mel, lengths):
     ''' device-event time of each kind's launches in one call '''
     marks = []
@@ -74,7 +92,9 @@ def per_kind_ms(voc, mel, lengths):
             marks.append((kind_of(a), s, e))
             return out
         return f
-    conv, up, post = voc._conv, voc._upsample, voc._post
+    conv, up, post, fed = voc._conv, voc._upsample, voc._post, voc._fed
+    if voc.bigvgan:
+        voc._fed = wrap(fed, lambda a: 'snake')
     voc._conv = wrap(conv, lambda a: 'conv_pre' if a[0] == 'conv_pre' else f'resblock_c{a[1].shape[2]}')
     voc._upsample = wrap(up, lambda a: 'upsample')
     voc._post = wrap(post, lambda a: 'conv_post')
@@ -82,7 +102,7 @@ def per_kind_ms(voc, mel, lengths):
         voc(mel, lengths)
         torch.cuda.synchronize()
     finally:
-        voc._conv, voc._upsample, voc._post = conv, up, post
+        voc._conv, voc._upsample, voc._post, voc._fed = conv, up, post, fed
     out = {}
     for kind, s, e in marks:
         out[kind] = out.get(kind, 0.) + s.elapsed_time(e)
@@ -93,6 +113,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--batch', type=int, default=256)
+    ap.add_argument('--bigvgan', action='store_true', help='also measure a BigVGAN generator of the base layout (V1 + snakebeta)')
     args = ap.parse_args()
     import bench
     from daft_exprt import griffin_lim as G
@@ -120,18 +141,21 @@ def main():
     weights = O.make_weights(cfg, seed_mel, (12,), seed=0)
     audio_s = frames * cfg['hop_size'] / cfg['sampling_rate']
     out = {'metric': 'hifi_gan_vocoder', 'config': 'V1', 'batch': B, 'T_max': T, 'mel_frames': frames, 'audio_seconds': audio_s}
-    for dtype in ('bf16', 'fp32'):
-        voc = Vocoder(cfg, O.state_dict(weights), compute_dtype=dtype, device=dev)
+
+    def measure(cfg, state, dtype):
+        voc = Vocoder(cfg, state, compute_dtype=dtype, device=dev)
         voc.check_hparams(hp)
         voc(mel, lengths)                                                    # warm-up: code objects, the workspace
         torch.cuda.synchronize()
         ms, (wavs, _) = _timed(lambda: voc(mel, lengths), args.reps)
         kinds = per_kind_ms(voc, mel, lengths)
         costs = layer_costs(cfg, frames, 2 if dtype == 'bf16' else 4)
+        if voc.bigvgan:
+            costs['snake'] = snake_cost(cfg, frames)
         layers = {}
         for kind, (flop, byts) in costs.items():
             t = kinds[kind] * 1e-3
-            peak = PEAK['fp32'] if kind == 'conv_post' else PEAK[dtype]     # conv_post is a VALU reduction in either mode
+            peak = PEAK['fp32'] if kind in ('conv_post', 'snake') else PEAK[dtype]   # VALU work in either mode
             t_c, t_m = flop / peak, byts / PEAK_HBM
             layers[kind] = {'gflop': flop / 1e9, 'gbytes': byts / 1e9, 'flop_per_byte': flop / byts, 'ms': kinds[kind],
                             'tflops': flop / t / 1e12, 'tbps': byts / t / 1e12, 'bound': 'compute' if t_c >= t_m else 'HBM',
@@ -139,11 +163,25 @@ def main():
         wide = [k for k in layers if k.startswith('resblock_c') and int(k[len('resblock_c'):]) >= 128]
         wide_flop, wide_s = sum(costs[k][0] for k in wide), sum(kinds[k] for k in wide) * 1e-3
         total_flop = sum(f for f, _ in costs.values())
-        out[dtype] = {'ms_per_call': ms, 'audio_s_per_wall_s': audio_s / (ms * 1e-3), 'tflop': total_flop / 1e12,
-                      'tflops_end_to_end': total_flop / (ms * 1e-3) / 1e12, 'peak_abs': float(wavs.abs().max()),
-                      'wide_stages_share_of_mfma_peak': wide_flop / wide_s / PEAK[dtype] if wide else None, 'layers': layers}
+        res = {'ms_per_call': ms, 'audio_s_per_wall_s': audio_s / (ms * 1e-3), 'tflop': total_flop / 1e12,
+               'tflops_end_to_end': total_flop / (ms * 1e-3) / 1e12, 'peak_abs': float(wavs.abs().max()),
+               'wide_stages_share_of_mfma_peak': wide_flop / wide_s / PEAK[dtype] if wide else None, 'layers': layers}
+        if voc.bigvgan:
+            res['snake_share_of_call'] = kinds['snake'] / sum(kinds.values())
+            res['snake_rate_over_float4_copy'] = layers['snake']['tbps'] * 1e12 / COPY_RATE
         del voc
         torch.cuda.empty_cache()
+        return res
+    for dtype in ('bf16', 'fp32'):
+        out[dtype] = measure(cfg, O.state_dict(weights), dtype)
+    if args.bigvgan:
+        from tests import bigvgan_oracle as BG
+        big = dict(cfg, activation='snakebeta', snake_logscale=True)
+        big_weights, raw, _, filters = BG.make_weights(big, seed_mel, (12,), seed=0)
+        state = BG.state_dict(big, big_weights, raw, filters, form='plain')
+        out['bigvgan'] = {'config': 'V1 + snakebeta'}
+        for dtype in ('bf16', 'fp32'):
+            out['bigvgan'][dtype] = measure(big, state, dtype)
     G.griffin_lim_batch(mel, lengths, hp)
     torch.cuda.synchronize()
     out['griffin_lim_preview_ms'], _ = _timed(lambda: G.griffin_lim_batch(mel, lengths, hp), args.reps)

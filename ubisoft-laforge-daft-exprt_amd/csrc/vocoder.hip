@@ -11,6 +11,7 @@
 //                    j = j0 + s u, j0 = (p + pad) mod u, of input rows t + (p + pad) div u - s.  Weights [phase][s][Cout][Cin], zero
 //                    where j >= k (phases of unequal length, e.g. k 7, u 3).
 //   dx_voc_post      leaky-ReLU 0.01, 7-tap conv to one channel, tanh: a reduction on the VALU, fp32 throughout.
+//                    dx_vocoder_post_clamp is the same kernel with clamp(-1, 1) in place of tanh (BigVGAN's `use_tanh_at_final` off).
 // Sequence ends: rows < 0 or >= n[b] of the input are zeros and are never read; output rows >= n[b] (x u) are written as zeros up
 // to the padded extent.  No atomics, no split-K: every output element is one k-ordered chain in one lane, whatever the batch.
 // Channel counts that are no multiple of 32 (and taps whose span exceeds the staged halo) run a plain VALU kernel of the same
@@ -169,6 +170,7 @@ __global__ __launch_bounds__(256) void voc_conv_valu_kernel(VocArgs a) {
 struct VocPostArgs { const float* x; const float* w; const float* bias; float* y; const int64_t* n; long ldx, ldy; int N, C, taps; float slope; };
 
 // grid (ceil(N / 256), B): one thread per output sample; 16-byte loads when C and ldx are multiples of 4
+template <bool CLAMP>
 __global__ __launch_bounds__(256) void voc_post_kernel(VocPostArgs a) {
   const int b = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
   if (t >= a.N) return;
@@ -193,7 +195,8 @@ __global__ __launch_bounds__(256) void voc_post_kernel(VocPostArgs a) {
         for (int c = 0; c < a.C; ++c) s = fmaf(voc_lrelu(xr[c], a.slope), wr[c], s);
       }
     }
-    out = tanhf(s + (a.bias ? a.bias[0] : 0.f));
+    s += a.bias ? a.bias[0] : 0.f;
+    out = CLAMP ? fminf(fmaxf(s, -1.f), 1.f) : tanhf(s);
   }
   a.y[(long)b * a.ldy + t] = out;
 }
@@ -222,6 +225,19 @@ int voc_launch(const VocArgs& a, int w_dtype, int B, void* stream, const char* w
     if (w_dtype == DX_BF16) hipLaunchKernelGGL(voc_conv_valu_kernel<bf16_t>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(voc_conv_valu_kernel<float>, grid, dim3(256), 0, s, a);
   }
+  DX_LAUNCH_CHECK();
+  return DX_OK;
+}
+
+template <bool CLAMP>
+int voc_post_launch(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, const int64_t* n_rows, int B, int N,
+                    int C, int taps, float in_slope, void* stream, const char* who) {
+  DX_REQUIRE(x && w && y && n_rows, DX_ERR_ARG, "%s: null pointer", who);
+  DX_REQUIRE(B > 0 && B <= 65535 && N > 0 && C > 0 && taps > 0 && taps % 2 == 1 && ldx >= C && ldy >= N, DX_ERR_SHAPE,
+             "%s: bad shape B=%d N=%d C=%d taps=%d ldx=%ld ldy=%ld", who, B, N, C, taps, ldx, ldy);
+  DX_REQUIRE(voc_aligned16(x), DX_ERR_ARG, "%s: x must be 16-byte aligned", who);
+  VocPostArgs a = {x, w, bias, y, n_rows, ldx, ldy, N, C, taps, in_slope};
+  hipLaunchKernelGGL(voc_post_kernel<CLAMP>, dim3(dx_cdiv(N, 256), B), dim3(256), 0, (hipStream_t)stream, a);
   DX_LAUNCH_CHECK();
   return DX_OK;
 }
@@ -261,12 +277,10 @@ extern "C" int dx_voc_upsample(const float* x, long ldx, const void* w_packed, i
 
 extern "C" int dx_voc_post(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, const int64_t* n_rows,
                            int B, int N, int C, int taps, float in_slope, void* stream) {
-  DX_REQUIRE(x && w && y && n_rows, DX_ERR_ARG, "dx_voc_post: null pointer");
-  DX_REQUIRE(B > 0 && B <= 65535 && N > 0 && C > 0 && taps > 0 && taps % 2 == 1 && ldx >= C && ldy >= N, DX_ERR_SHAPE,
-             "dx_voc_post: bad shape B=%d N=%d C=%d taps=%d ldx=%ld ldy=%ld", B, N, C, taps, ldx, ldy);
-  DX_REQUIRE(voc_aligned16(x), DX_ERR_ARG, "dx_voc_post: x must be 16-byte aligned");
-  VocPostArgs a = {x, w, bias, y, n_rows, ldx, ldy, N, C, taps, in_slope};
-  hipLaunchKernelGGL(voc_post_kernel, dim3(dx_cdiv(N, 256), B), dim3(256), 0, (hipStream_t)stream, a);
-  DX_LAUNCH_CHECK();
-  return DX_OK;
+  return voc_post_launch<false>(x, ldx, w, bias, y, ldy, n_rows, B, N, C, taps, in_slope, stream, "dx_voc_post");
+}
+
+extern "C" int dx_vocoder_post_clamp(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy,
+                                     const int64_t* n_rows, int B, int N, int C, int taps, float in_slope, void* stream) {
+  return voc_post_launch<true>(x, ldx, w, bias, y, ldy, n_rows, B, N, C, taps, in_slope, stream, "dx_vocoder_post_clamp");
 }

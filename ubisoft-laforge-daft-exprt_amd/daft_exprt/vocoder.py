@@ -10,7 +10,21 @@ Weight norm is folded once at load time (float64, plain torch: plumbing); every 
 (`dx_voc_conv`, `dx_voc_upsample`, `dx_voc_post`) on time-major fp32 activations with bf16 or fp32 MFMA operands.  Sequence ends
 follow the dead-row contract: every layer treats the rows past an utterance's end as zeros without reading them, so an utterance
 gets the same bits alone, in a ragged batch and in any sub-batch.  No CPU fallback: without the HIP library / a GPU this raises.
+
+A config with `"activation": "snake"` or `"snakebeta"` is a BigVGAN generator (Lee et al. 2023; same checkpoint layout): the same
+convolutions, with every leaky-ReLU replaced by an anti-aliased periodic activation -- csrc/snake.hip (`dx_vocoder_snake`), one launch
+into one more workspace buffer in front of every conv, which then runs with in_slope 1 -- none in front of the transposed convs, and
+tanh or a clamp at the end:
+
+    per stage i:  x = ups.i(x);  x = mean_j AMPBlock[i * nk + j](x)     AMPBlock1: r += convs2.m(act[2 m + 1](convs1.m(act[2 m](r))))
+    wav = tanh | clamp(conv_post(act_post(x)))                          AMPBlock2: r += convs.m(act[m](r))
+
+Its channel counts are zero-padded to multiples of 32 (zero weights and biases, alpha 1 and 1 / beta 0 on the padding, which
+therefore stays exactly zero through every layer), so that the 48- and 24-channel tail of the 1536-channel models runs on MFMA too.
+No upstream BigVGAN file or source was at hand when this was written: key names, pad geometry and the filter formula are restated
+from the released code from memory and tested against that restatement (tests/bigvgan_oracle.py) only.
 """
+import ctypes
 import json
 import math
 import os
@@ -25,6 +39,8 @@ POST_SLOPE = 0.01           # F.leaky_relu's default in front of conv_post (mode
 DEFAULT_WORKSPACE_BYTES = 8 << 30
 _CONFIG_LISTS = ('upsample_rates', 'upsample_kernel_sizes', 'resblock_kernel_sizes', 'resblock_dilation_sizes')
 _CONFIG_KEYS = ('resblock',) + _CONFIG_LISTS + ('upsample_initial_channel', 'num_mels', 'hop_size', 'sampling_rate')
+_ACTIVATIONS = ('snake', 'snakebeta')
+FILTER_TAPS = 12            # of the 2x resamplers around BigVGAN's activations (upstream's Activation1d defaults)
 
 
 def load_config(config):
@@ -42,6 +58,9 @@ def validate_config(cfg):
             raise ValueError(f'vocoder config: "{key}" is missing')
     if str(cfg['resblock']) not in ('1', '2'):
         raise ValueError(f'vocoder config: "resblock" is {cfg["resblock"]!r}, expected "1" or "2"')
+    if cfg.get('activation') is not None and cfg['activation'] not in _ACTIVATIONS:
+        raise ValueError(f'vocoder config: "activation" is {cfg["activation"]!r}, expected "snake" or "snakebeta" (a BigVGAN '
+                         f'generator) or no such key (HiFi-GAN)')
     for key in _CONFIG_LISTS:
         if not isinstance(cfg[key], (list, tuple)) or len(cfg[key]) == 0:
             raise ValueError(f'vocoder config: "{key}" must be a non-empty list')
@@ -107,18 +126,96 @@ def folded_weight(state_dict, name):
 def folded_state(cfg, state_dict):
     ''' {name: (weight float64, bias float64)} of every layer, shapes checked against the config '''
     out = {}
-    for name, _, shape, _ in layer_table(cfg):
+    for layer, _, shape, _ in layer_table(cfg):
+        name = layer
+        if is_bigvgan(cfg) and layer.startswith('ups.') and any(key.startswith(f'{layer}.0.') for key in state_dict):
+            name = f'{layer}.0'                                     # BigVGAN wraps each transposed conv in a ModuleList
         w = folded_weight(state_dict, name)
         if tuple(w.shape) != shape:
             raise ValueError(f'vocoder checkpoint: "{name}" weight has shape {tuple(w.shape)}, the config gives {shape}')
+        n_out = shape[1] if layer.startswith('ups.') else shape[0]
+        if layer == 'conv_post' and is_bigvgan(cfg) and not cfg.get('use_bias_at_final', True):
+            out[layer] = (w, torch.zeros((n_out,), dtype=torch.float64))
+            continue
         if f'{name}.bias' not in state_dict:
             raise ValueError(f'vocoder checkpoint: "{name}.bias" is missing')
         b = state_dict[f'{name}.bias'].detach().double().cpu()
-        n_out = shape[1] if name.startswith('ups.') else shape[0]
         if tuple(b.shape) != (n_out,):
             raise ValueError(f'vocoder checkpoint: "{name}.bias" has shape {tuple(b.shape)}, expected ({n_out},)')
-        out[name] = (w, b)
+        out[layer] = (w, b)
     return out
+
+
+def is_bigvgan(cfg):
+    return cfg.get('activation') is not None
+
+
+def activation_table(cfg):
+    ''' [(layer the activation feeds, the activation's state-dict name)] of a BigVGAN generator in forward order: in an AMPBlock1
+        activations[2 m] feeds convs1[m] and activations[2 m + 1] convs2[m], in an AMPBlock2 activations[m] feeds convs[m] '''
+    out = []
+    for layer, _, _, _ in layer_table(cfg):
+        if layer.startswith('resblocks.'):
+            block, convs, m = layer.rsplit('.', 2)
+            a = {'convs1': 2 * int(m), 'convs2': 2 * int(m) + 1, 'convs': int(m)}[convs]
+            out.append((layer, f'{block}.activations.{a}'))
+    return out + [('conv_post', 'activation_post')]
+
+
+def kaiser_sinc_filter(cutoff=0.25, half_width=0.3, kernel_size=FILTER_TAPS):
+    ''' the low-pass of BigVGAN's 2x resamplers, float64 (kernel_size,): a symmetric Kaiser window (beta from the transition width
+        4 half_width) times 2 cutoff sinc(2 cutoff t), t = -(kernel_size - 1) / 2 ..., normalised to sum 1 '''
+    half = kernel_size // 2
+    a = 2.285 * (half - 1) * math.pi * 4. * half_width + 7.95
+    beta = 0.1102 * (a - 8.7)                                         # Kaiser's rule for a > 50 (a = 51.02 here)
+    t = torch.arange(-half, half, dtype=torch.float64) + 0.5
+    f = 2. * cutoff * torch.kaiser_window(kernel_size, periodic=False, beta=beta, dtype=torch.float64) * torch.sinc(2. * cutoff * t)
+    return f / f.sum()
+
+
+def activation_state(cfg, state_dict, name, channels):
+    ''' (alpha', 1 / (beta' + 1e-9), f_up, f_down) of the activation `name`, float64: alpha' = exp(alpha) under `snake_logscale`,
+        beta' the same transform of `beta` (`snakebeta`) or alpha' itself (`snake`); the filters are the checkpoint's buffers where
+        it has them, `kaiser_sinc_filter()` otherwise '''
+    keys = ['alpha', 'beta'] if cfg['activation'] == 'snakebeta' else ['alpha']
+    raw = []
+    for key in keys:
+        if f'{name}.act.{key}' not in state_dict:
+            raise ValueError(f'vocoder checkpoint: "{name}.act.{key}" is missing')
+        v = state_dict[f'{name}.act.{key}'].detach().double().cpu()
+        if tuple(v.shape) != (channels,):
+            raise ValueError(f'vocoder checkpoint: "{name}.act.{key}" has shape {tuple(v.shape)}, expected ({channels},)')
+        raw.append(v.exp() if cfg.get('snake_logscale', False) else v)
+    filters = []
+    for key in (f'{name}.upsample.filter', f'{name}.downsample.lowpass.filter'):
+        if key in state_dict:
+            f = state_dict[key].detach().double().cpu()
+            if tuple(f.shape) != (1, 1, FILTER_TAPS):
+                raise ValueError(f'vocoder checkpoint: "{key}" has shape {tuple(f.shape)}, expected (1, 1, {FILTER_TAPS})')
+            filters.append(f.reshape(-1))
+        else:
+            filters.append(kaiser_sinc_filter())
+    return raw[0], 1. / (raw[-1] + 1e-9), filters[0], filters[1]
+
+
+def _pad32(c):
+    return -(-c // 32) * 32
+
+
+def pad_layer(name, kind, w, b, shape):
+    ''' a BigVGAN layer with its channel counts zero-padded to multiples of 32 -- all but conv_pre's mel bins (`pack_conv_weight`
+        pads those) and conv_post's single output: (weight, bias, shape) '''
+    cin_axis, cout_axis = (0, 1) if kind == 'up' else (1, 0)
+    padded = list(shape)
+    if name != 'conv_pre':
+        padded[cin_axis] = _pad32(shape[cin_axis])
+    if name != 'conv_post':
+        padded[cout_axis] = _pad32(shape[cout_axis])
+    wp = torch.zeros(padded, dtype=torch.float64)
+    wp[:shape[0], :shape[1]] = w
+    bp = torch.zeros((padded[cout_axis],), dtype=torch.float64)
+    bp[:b.numel()] = b
+    return wp, bp, tuple(padded)
 
 
 def pack_conv_weight(w, dtype, cin_pad=None):
@@ -216,11 +313,19 @@ class Vocoder:
         folded = folded_state(cfg, state_dict)
         dt = torch.bfloat16 if compute_dtype == 'bf16' else torch.float32
         self._wdt = H.BF16 if compute_dtype == 'bf16' else H.F32
+        self.bigvgan = is_bigvgan(cfg)
         # conv_pre on the MFMA kernel: its input channels (80 mel bins) are zero-padded to a multiple of 32
-        self.mel_channels = -(-self.num_mels // 32) * 32 if self.c0 % 32 == 0 else self.num_mels
-        self._layers = {}
+        self.mel_channels = _pad32(self.num_mels) if self.c0 % 32 == 0 or self.bigvgan else self.num_mels
+        # channels of conv_pre's output and of every stage; the activation in front of every conv but conv_pre / the transposed ones
+        self._chans = [_pad32(self.c0 >> i) if self.bigvgan else self.c0 >> i for i in range(len(self.rates) + 1)]
+        self._slope, self._post_slope = (1., 1.) if self.bigvgan else (LRELU_SLOPE, POST_SLOPE)
+        self._final_clamp = self.bigvgan and not cfg.get('use_tanh_at_final', True)
+        self._buffers = 7 if self.bigvgan else 6
+        self._layers, self._acts = {}, {}
         for name, kind, shape, dil in layer_table(cfg):
             w, b = folded[name]
+            if self.bigvgan:
+                w, b, shape = pad_layer(name, kind, w, b, shape)
             if name == 'conv_post':
                 packed = w[0].t().contiguous().float()                                    # [tap][C] fp32
             elif kind == 'up':
@@ -228,7 +333,16 @@ class Vocoder:
             else:
                 packed = pack_conv_weight(w, dt, self.mel_channels if name == 'conv_pre' else None)
             self._layers[name] = (packed.to(self.device), b.float().to(self.device), shape, dil)
-        self._ws = None
+        if self.bigvgan:
+            live = {name: shape[1] for name, _, shape, _ in layer_table(cfg)}
+            for layer, name in activation_table(cfg):
+                alpha, inv_beta, f_up, f_down = activation_state(cfg, state_dict, name, live[layer])
+                c = self._layers[layer][2][1]
+                a, ib = torch.ones((c,), dtype=torch.float64), torch.zeros((c,), dtype=torch.float64)
+                a[:live[layer]], ib[:live[layer]] = alpha, inv_beta
+                taps = (ctypes.c_float * (2 * FILTER_TAPS))(*f_up.tolist(), *f_down.tolist())      # host side: kernel arguments
+                self._acts[layer] = (a.float().to(self.device), ib.float().to(self.device), taps)
+        self._ws = self._act = None
 
     @classmethod
     def from_checkpoint(cls, path, config=None, compute_dtype='bf16', device=None):
@@ -251,9 +365,22 @@ class Vocoder:
             raise ValueError(f'vocoder "sampling_rate" is {self.sampling_rate}, hparams.sampling_rate is {hparams.sampling_rate}')
 
     # ---- launches ---------------------------------------------------------------------------------------------------------
-    def _conv(self, name, x, y, n, res=None, acc=None, acc_scale=0., acc_init=False, slope=LRELU_SLOPE):
+    def _fed(self, name, x, n):
+        ''' what the layer `name` reads: x itself (HiFi-GAN: the leaky-ReLU is applied as the conv stages its input), or BigVGAN's
+            activation of x, written to the workspace's seventh buffer '''
+        if not self.bigvgan:
+            return x
+        alpha, inv_beta, taps = self._acts[name]
+        B, N, c = x.shape
+        y = self._act[:B * N * c].view(B, N, c)
+        H.check(H.lib().dx_vocoder_snake(H.ptr(x), c, H.ptr(alpha), H.ptr(inv_beta), ctypes.addressof(taps), H.ptr(y), c, H.ptr(n), B, N, c,
+                                         H.stream()))
+        return y
+
+    def _conv(self, name, x, y, n, res=None, acc=None, acc_scale=0., acc_init=False, slope=None):
         w, b, (cout, cin, k), dil = self._layers[name]
         B, N, ldx = x.shape
+        slope = self._slope if slope is None else slope
         H.check(H.lib().dx_voc_conv(H.ptr(x), ldx, H.ptr(w), self._wdt, H.ptr(b), H.ptr(res), cout, H.ptr(y), cout, H.ptr(acc), cout,
                                     float(acc_scale), int(acc_init), H.ptr(n), B, N, w.shape[2], cout, k, dil, float(slope), H.stream()))
 
@@ -261,45 +388,47 @@ class Vocoder:
         w, b, (cin, cout, k), _ = self._layers[name]
         B, N, _ = x.shape
         H.check(H.lib().dx_voc_upsample(H.ptr(x), cin, H.ptr(w), self._wdt, H.ptr(b), H.ptr(y), cout, H.ptr(n), B, N, cin, cout, k, u,
-                                        LRELU_SLOPE, H.stream()))
+                                        self._slope, H.stream()))
 
     def _post(self, x, out, n):
         w, bias, _, _ = self._layers['conv_post']
         B, N, c = x.shape
-        H.check(H.lib().dx_voc_post(H.ptr(x), c, H.ptr(w), H.ptr(bias), H.ptr(out), out.stride(0), H.ptr(n), B, N, c, 7, POST_SLOPE,
-                                    H.stream()))
+        post = H.lib().dx_vocoder_post_clamp if self._final_clamp else H.lib().dx_voc_post
+        H.check(post(H.ptr(x), c, H.ptr(w), H.ptr(bias), H.ptr(out), out.stride(0), H.ptr(n), B, N, c, 7, self._post_slope, H.stream()))
 
     def _elements_per_utterance(self, T):
         ''' (floats of the largest activation of one utterance of T frames, floats of its padded mel) '''
-        rows, most = T, T * self.c0
+        rows, most = T, T * self._chans[0]
         for i, u in enumerate(self.rates):
             rows *= u
-            most = max(most, rows * (self.c0 >> (i + 1)))
+            most = max(most, rows * self._chans[i + 1])
         return most, T * self.mel_channels
 
     def _run(self, mel, lengths, out, T):
         ''' one sub-batch: mel (b, num_mels, >= T), lengths (b,) clamped to [0, T], out (b, >= T * hop) '''
         b = mel.shape[0]
         most, mel_el = self._elements_per_utterance(T)
-        need = b * (6 * most + mel_el)
+        nb = self._buffers
+        need = b * (nb * most + mel_el)
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.float32, device=self.device)
         if _config.POISON:
             self._ws.fill_(float('nan'))
-        bufs = [self._ws[i * b * most:(i + 1) * b * most] for i in range(6)]
-        melt = self._ws[6 * b * most:need].view(b, T, self.mel_channels)
+        bufs = [self._ws[i * b * most:(i + 1) * b * most] for i in range(nb)]
+        melt = self._ws[nb * b * most:need].view(b, T, self.mel_channels)
         melt[:, :, :self.num_mels] = mel[:, :, :T].transpose(1, 2)
         if self.mel_channels > self.num_mels:
             melt[:, :, self.num_mels:] = 0.
         view = lambda buf, rows, c: buf[:b * rows * c].view(b, rows, c)      # noqa: E731
-        x, up, ping, pong, tmp, total = bufs
-        rows, c, n = T, self.c0, lengths
+        x, up, ping, pong, tmp, total = bufs[:6]
+        self._act = bufs[6] if self.bigvgan else None
+        rows, c, n = T, self._chans[0], lengths
         xv = view(x, rows, c)
         self._conv('conv_pre', melt, xv, n, slope=1.)
         nk = len(self.res_kernels)
         for i, u in enumerate(self.rates):
-            c_out = c >> 1
+            c_out = self._chans[i + 1]
             upv = view(up, rows * u, c_out)
             self._upsample(f'ups.{i}', xv, upv, n, u)
             rows, c, n = rows * u, c_out, n * u
@@ -311,21 +440,22 @@ class Vocoder:
                     last = m == len(dils) - 1
                     tail = dict(res=cur, acc=sv if last else None, acc_scale=1. / nk, acc_init=j == 0)
                     if self.resblock == '1':
-                        self._conv(f'{block}.convs1.{m}', cur, tv, n)
-                        self._conv(f'{block}.convs2.{m}', tv, None if last else nxt, n, **tail)
+                        self._conv(f'{block}.convs1.{m}', self._fed(f'{block}.convs1.{m}', cur, n), tv, n)
+                        self._conv(f'{block}.convs2.{m}', self._fed(f'{block}.convs2.{m}', tv, n), None if last else nxt, n, **tail)
                     else:
-                        self._conv(f'{block}.convs.{m}', cur, None if last else nxt, n, **tail)
+                        self._conv(f'{block}.convs.{m}', self._fed(f'{block}.convs.{m}', cur, n), None if last else nxt, n, **tail)
                     cur = nxt
             x, total = total, x
             xv = view(x, rows, c)
-        self._post(xv, out, n)
+        self._post(self._fed('conv_post', xv, n), out, n)
 
     def __call__(self, mel, lengths, max_workspace_bytes=DEFAULT_WORKSPACE_BYTES):
         ''' mel (B, num_mels, T) natural-log mel on the device (what `inference` returns as `decoder_preds[0]`; columns at or
             past `lengths` may hold anything, they are not read), lengths (B,) int64.
             Returns (wavs (B, T * hop) fp32 in [-1, 1] with zeros past n_samples, n_samples = lengths * hop (B,) int64).
             The activations of the last stage are large (about 8 GB for one fp32 tensor at B = 256, T = 950), so the batch is
-            walked in sub-batches whose workspace -- six activation buffers of the largest stage plus the padded mel -- stays
+            walked in sub-batches whose workspace -- six activation buffers of the largest stage (seven for a BigVGAN generator:
+            one more for its activations' output) plus the padded mel -- stays
             under `max_workspace_bytes` (default 8 GB; one utterance at a time when even that does not fit).  The workspace is
             kept and reused across calls; results do not depend on the split. '''
         H.require_gpu(mel, lengths)
@@ -345,7 +475,7 @@ class Vocoder:
                 while b1 < B:                                             # greedy: as many utterances as fit under the cap
                     t_new = max(t_sub, host[b1])
                     most, mel_el = self._elements_per_utterance(t_new)
-                    if b1 > b0 and 4 * (b1 + 1 - b0) * (6 * most + mel_el) > max_workspace_bytes:
+                    if b1 > b0 and 4 * (b1 + 1 - b0) * (self._buffers * most + mel_el) > max_workspace_bytes:
                         break
                     b1, t_sub = b1 + 1, t_new
                 self._run(mel[b0:b1], lengths[b0:b1].contiguous(), wavs[b0:b1], t_sub)

@@ -270,7 +270,11 @@ class _ConvList(nn.Module):
 
 def trainable_stages(cfg):
     ''' raises ValueError naming the first layer whose channel counts the MFMA kernels do not take (multiples of 32; conv_pre's
-        mel bins are zero-padded, conv_post's single output is torch) '''
+        mel bins are zero-padded, conv_post's single output is torch), or the `activation` of a BigVGAN config: its anti-aliased
+        activation has a forward kernel only (inference: `vocoder.Vocoder`) '''
+    if cfg.get('activation') is not None:
+        raise ValueError(f'vocoder training: the config\'s "activation" is {cfg["activation"]!r}: fine-tuning covers HiFi-GAN generators '
+                         f'only, a BigVGAN generator can be loaded for inference (daft_exprt.vocoder.Vocoder) but not trained')
     for name, kind, shape, _ in V.layer_table(cfg):
         cin, cout = (shape[0], shape[1]) if kind == 'up' else (shape[1], shape[0])
         bad = [c for c, skip in ((cin, name == 'conv_pre'), (cout, name == 'conv_post')) if not skip and c % 32]
