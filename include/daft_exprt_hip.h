@@ -165,6 +165,19 @@ int dx_conv1d_lnbwd(const void* x, int x_dtype, long ldx, const void* w_packed, 
 enum { DX_LN_PATH_SPLITK = 0, DX_LN_PATH_PLAN_K3 = 1, DX_LN_PATH_PLAN_K1 = 2, DX_LN_PATH_ROWS128 = 3, DX_LN_PATH_ROWS64 = 4 };
 int dx_conv1d_ln_path(int x_dtype, int w_dtype, int taps, int Cin, int B, int N, int has_plan, int has_frag, int backward);
 
+/* Which kernel dx_conv1d / dx_conv1d_wfrag runs a GEMM on: the ONE statement of that policy, as dx_conv1d_ln_path is for the
+ * LayerNorm-fused entry points.  Host-only: launches nothing, touches no device.  It classifies and does not validate (the entry
+ * points still reject what they reject).  ldx / ldy / flags as the entry points take them.  Additive (the ABI version stays).
+ *   DX_PLAIN_PATH_WREG     conv_wreg_kernel, weights in registers: bf16 x and w, Cin = 128, Cout % 256 == 0, row strides multiples
+ *                          of 8, N * ld within 32-bit byte offsets, neither DX_CONV_TRANSPOSED_OUT nor DX_CONV_ACCUMULATE
+ *   DX_PLAIN_PATH_ROWS64   conv_gemm_kernel on 64-row tiles: one channel tile (Cout <= 128) with taps = 1, or with B * N <= 64000
+ *   DX_PLAIN_PATH_ROWS128  ... on 128-row tiles: one channel tile with taps = 3 and B * N > 64000; every other GEMM with Cout > 128
+ *   DX_PLAIN_PATH_ROWS256  ... on 256-row tiles: Cout > 128, taps = 3, Cin >= 512, bf16 weights and
+ *                          ceil(N / 256) * B * ceil(Cout / 128) >= 1024 workgroups (the environment variable DX_CONV_WIDE_MI, read once,
+ *                          replaces that last condition: 4 = always, 1 = 64-row tiles, any other value = 128-row tiles) */
+enum { DX_PLAIN_PATH_WREG = 0, DX_PLAIN_PATH_ROWS64 = 1, DX_PLAIN_PATH_ROWS128 = 2, DX_PLAIN_PATH_ROWS256 = 3 };
+int dx_conv1d_plain_path(int x_dtype, int w_dtype, int y_dtype, int taps, int Cin, int Cout, int B, int N, long ldx, long ldy, int flags);
+
 /* The weights of a k = 3 conv in MFMA-fragment order: out[chunk][tap][half][block][lane][8] = w_packed[tap][32 block + (lane & 31)]
  * [32 chunk + 16 half + 8 (lane >> 5) + 0..7], block < Cout / 32; w_packed = the [3][Cout][Cin] bf16 packing of dx_pack_conv_weight
  * (either orientation), Cin and Cout multiples of 32.  A fragment (the B operand of one v_mfma_f32_32x32x16_bf16) is one contiguous

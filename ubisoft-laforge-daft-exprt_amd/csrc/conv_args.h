@@ -46,8 +46,8 @@ struct ConvArgs {
 // ---- host launchers, one kernel unit each; hidden: they are no part of the library's interface
 #define DX_HIDDEN __attribute__((visibility("hidden")))
 // conv_gemm_plain.hip: conv_gemm_kernel without LayerNorm, every dtype combination of dx_conv1d (DX_ERR_DTYPE otherwise)
-// (gd: the gate's dtype, or y_dtype when there is none), and the 64- / 128-row tile rule of the narrow k = 3 GEMMs (1 / 2), which
-// dx_conv1d_ln_path shares
+// (gd: the gate's dtype, or y_dtype when there is none) on the path dx_conv1d_plain_path names, and the 64- / 128-row tile rule of
+// the narrow k = 3 GEMMs (1 / 2), which dx_conv1d_ln_path shares
 DX_HIDDEN int conv_plain_launch(const ConvArgs& a, int x_dtype, int w_dtype, int y_dtype, int gd, int taps, hipStream_t s);
 DX_HIDDEN int conv_narrow_mi(int B, int N);
 // conv_gemm_ln.hip / conv_gemm_lnbwd.hip: conv_gemm_kernel with the forward / backward LayerNorm epilogue on `path`, any value of
@@ -56,6 +56,8 @@ DX_HIDDEN int conv_ln_launch(const ConvArgs& a, int path, int x_dtype, int w_dty
 DX_HIDDEN int conv_lnbwd_launch(const ConvArgs& a, int path, int x_dtype, int w_dtype, int taps, hipStream_t s);
 // conv_wreg.hip: bf16 operands, fp32 or bf16 output (and gate); false = shape not taken, nothing launched
 DX_HIDDEN bool conv_wreg_try(const ConvArgs& a, bool bf16_out, int taps, hipStream_t s);
+// ... and the shape / option rule of that kernel alone (bf16 x and w understood): host-only, what dx_conv1d_plain_path asks
+DX_HIDDEN bool conv_wreg_takes(int Cin, int Cout, int N, long ldx, long ldy, int flags);
 // conv_sk.hip: DX_LN_PATH_SPLITK, forward or backward by a.ln.enabled
 DX_HIDDEN int conv_sk_launch(const ConvArgs& a, hipStream_t s);
 // conv_wide.hip

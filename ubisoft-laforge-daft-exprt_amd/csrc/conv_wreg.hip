@@ -364,8 +364,7 @@ __global__ __launch_bounds__(WR_THREADS, 2) void conv_wreg_kernel(ConvArgs p, in
 // activations and weights are bf16; TO / TG: output and gate type.  false = shape not taken, nothing launched
 template <typename TO, typename TG>
 bool try_weight_stationary(const ConvArgs& a, int taps, hipStream_t s) {
-  if (a.ln.enabled || (a.flags & (DX_CONV_TRANSPOSED_OUT | DX_CONV_ACCUMULATE))) return false;
-  if (a.Cin != 128 || a.Cout % WR_BN || a.ldy % 8 || a.ldx % 8) return false;
+  if (a.ln.enabled || !conv_wreg_takes(a.Cin, a.Cout, a.N, a.ldx, a.ldy, a.flags)) return false;
   const int ztiles = a.Cout / WR_BN;
   // about one workgroup per CU; more position groups than tiles only adds weight loads
   const long tiles = (long)dx_cdiv(a.N, WR_BM) * a.B;
@@ -374,7 +373,6 @@ bool try_weight_stationary(const ConvArgs& a, int taps, hipStream_t s) {
   if (ngrp < 1) ngrp = 1;
   dim3 grid(ngrp * ztiles), block(WR_THREADS);
   const bool relu = a.flags & DX_CONV_RELU, gate = a.gate != nullptr;
-  if ((size_t)a.N * a.ldy * 4 >= (1ull << 32) || (size_t)a.N * a.ldx * 2 >= (1ull << 32)) return false;   // 32-bit buffer offsets
   if (a.relu_bits || a.gate_bits) {   // dx_conv1d_relu_bits: one bit per element written by the ReLU / read as the gate
     if constexpr (sizeof(TO) == 2) {
       if (taps != 3 || gate || (a.relu_bits != nullptr) == (a.gate_bits != nullptr) || (a.relu_bits && !relu) || (a.gate_bits && relu)) return false;
@@ -398,6 +396,14 @@ bool try_weight_stationary(const ConvArgs& a, int taps, hipStream_t s) {
 }
 
 }  // namespace
+
+// the shapes and epilogue options conv_wreg_kernel takes (bf16 operands): a pure predicate, shared by the launcher above and
+// dx_conv1d_plain_path
+bool conv_wreg_takes(int Cin, int Cout, int N, long ldx, long ldy, int flags) {
+  if (flags & (DX_CONV_TRANSPOSED_OUT | DX_CONV_ACCUMULATE)) return false;
+  if (Cin != 128 || Cout <= 0 || Cout % WR_BN || ldy % 8 || ldx % 8) return false;
+  return (size_t)N * ldy * 4 < (1ull << 32) && (size_t)N * ldx * 2 < (1ull << 32);   // 32-bit buffer offsets
+}
 
 bool conv_wreg_try(const ConvArgs& a, bool bf16_out, int taps, hipStream_t s) {
   return bf16_out ? try_weight_stationary<bf16_t, bf16_t>(a, taps, s) : try_weight_stationary<float, float>(a, taps, s);

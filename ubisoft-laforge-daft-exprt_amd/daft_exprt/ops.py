@@ -95,11 +95,16 @@ def pack_conv_weight(w, dtype, transpose_flip=False, out=None):
     return out
 
 
-# Which kernel a GEMM runs on is decided on the C side (csrc/conv_gemm.hip and the launchers of the kernel units behind it).  For the LayerNorm-fused GEMMs `ln_path` asks that decision
-# (dx_conv1d_ln_path) and nothing here restates it.  The wide and the register-weights kernel have no host query: their shape rules are
-# stated once each below (tests/test_gpu_conv.py asserts the predicates and then runs the entry points, which check the same on their side).
+# Which kernel a GEMM runs on is decided on the C side (csrc/conv_gemm.hip and the launchers of the kernel units behind it).  For the
+# LayerNorm-fused GEMMs `ln_path` asks that decision (dx_conv1d_ln_path), for dx_conv1d / dx_conv1d_wfrag `plain_path` does
+# (dx_conv1d_plain_path: the register-weights kernel or the tiled kernel's 64 / 128 / 256-row tiles), and nothing here restates either.
+# The wide kernel is chosen HERE, by `conv1d` (w_frag + wide_plan on a `wide_shape_ok` shape), and the entry point checks the same shape
+# rule on its side; `wreg_shape_ok` is the shape part of the register-weights rule for callers that decide which fragment-order copies to
+# keep -- whether a given call runs on that kernel is `plain_path`'s answer (row strides, flags and operand types count too).
 LN_SPLITK, LN_PLAN_K3, LN_PLAN_K1, LN_ROWS128, LN_ROWS64 = range(5)    # DX_LN_PATH_* of include/daft_exprt_hip.h
+PLAIN_WREG, PLAIN_ROWS64, PLAIN_ROWS128, PLAIN_ROWS256 = range(4)       # DX_PLAIN_PATH_* of include/daft_exprt_hip.h
 _LN_PATHS = {}
+_PLAIN_PATHS = {}
 
 
 def ln_path(x_dtype, w_dtype, taps, Cin, B, N, has_plan, has_frag, backward=False):
@@ -110,6 +115,21 @@ def ln_path(x_dtype, w_dtype, taps, Cin, B, N, has_plan, has_frag, backward=Fals
     if v is None:
         v = _LN_PATHS[key] = H.lib().dx_conv1d_ln_path(H._DT[x_dtype], H._DT[w_dtype], taps, Cin, B, N, int(has_plan), int(has_frag),
                                                        int(backward))
+    return v
+
+
+def plain_path(x_dtype, w_dtype, y_dtype, taps, Cin, Cout, B, N, ldx=None, ldy=None, transposed_out=False, accumulate=False, relu=False):
+    ''' the kernel path of conv1d (without a wide plan) for these arguments: PLAIN_WREG / PLAIN_ROWS64 / PLAIN_ROWS128 / PLAIN_ROWS256.
+        ldx / ldy: the row strides of x and of the output (default: contiguous).  A pure function of its arguments and of the
+        environment variable the library reads once (DX_CONV_WIDE_MI): remembered, as `ln_path` '''
+    ldx = Cin if ldx is None else ldx
+    ldy = (N if transposed_out else Cout) if ldy is None else ldy
+    flags = (H.CONV_RELU if relu else 0) | (H.CONV_TRANSPOSED_OUT if transposed_out else 0) | (4 if accumulate else 0)
+    key = (x_dtype, w_dtype, y_dtype, taps, Cin, Cout, B, N, ldx, ldy, flags)
+    v = _PLAIN_PATHS.get(key)
+    if v is None:
+        v = _PLAIN_PATHS[key] = H.lib().dx_conv1d_plain_path(H._DT[x_dtype], H._DT[w_dtype], H._DT[y_dtype], taps, Cin, Cout, B, N, ldx, ldy,
+                                                             flags)
     return v
 
 
@@ -133,6 +153,15 @@ def relu_bits_ok(x, w_packed, out_dtype=None):
     taps, Cout, Cin = w_packed.shape
     return (x.is_cuda and taps == 3 and wreg_shape_ok(Cin, Cout) and x.dtype == torch.bfloat16 and w_packed.dtype == torch.bfloat16
             and (out_dtype or x.dtype) == torch.bfloat16 and x.stride(1) % 8 == 0)
+
+
+def row_stride(t):
+    ''' elements between two rows of a (B, rows, W) operand as the kernels address it (utterance b starts b * rows * stride in).  torch leaves
+        the stride of a one-row dimension arbitrary -- (B, N, 1).transpose(1, 2).contiguous() keeps stride(1) = 1 -- so a single row takes it
+        from the batch stride, or from the width '''
+    if t.shape[1] > 1:
+        return t.stride(1)
+    return t.stride(0) if t.shape[0] > 1 else t.shape[2]
 
 
 def conv1d(x, w_packed, bias=None, out_dtype=None, relu=False, relu_gate=None, mask_lengths=None,
@@ -179,10 +208,20 @@ def conv1d(x, w_packed, bias=None, out_dtype=None, relu=False, relu_gate=None, m
     if out is None:
         assert not accumulate
         out = _empty((B, Cout, N) if transposed_out else (B, N, Cout), dtype=out_dtype, device=x.device)
+    ldy = row_stride(out)
+    assert out.stride(2) == 1 and (B == 1 or out.stride(0) == out.shape[1] * ldy), 'out: rows and utterances must be evenly spaced'
+    if relu_gate is not None:
+        # the kernels read the gate at the OUTPUT's element offset (row stride ldy): a gate laid out otherwise would gate with other elements
+        mixed = (x.dtype, w_packed.dtype, out.dtype, relu_gate.dtype) == (torch.float32, torch.bfloat16, torch.float32, torch.bfloat16)
+        assert relu_gate.dtype == out.dtype or mixed, \
+            f'relu_gate: dtype {relu_gate.dtype} does not go with a {out.dtype} output (the same type, or a bf16 gate of an fp32 output of fp32 x and bf16 weights)'
+        assert tuple(relu_gate.shape) == tuple(out.shape) and relu_gate.stride(2) == 1 and row_stride(relu_gate) == ldy and \
+            (B == 1 or relu_gate.stride(0) == out.stride(0)), \
+            f'relu_gate: shape {tuple(relu_gate.shape)} / strides {relu_gate.stride()} differ from the output\'s {tuple(out.shape)} / {out.stride()}'
     flags = (H.CONV_RELU if relu else 0) | (H.CONV_TRANSPOSED_OUT if transposed_out else 0) | (4 if accumulate else 0)
     with _probe('conv_gemm', lambda: 2. * B * N * Cin * Cout * taps, N):
-      H.check(H.lib().dx_conv1d_wfrag(H.ptr(x), H.dt(x), x.stride(1), H.ptr(w_packed), H.dt(w_packed), H.ptr(frag), H.ptr(bias),
-                                    H.ptr(out), H.dt(out), out.stride(1), H.ptr(relu_gate),
+      H.check(H.lib().dx_conv1d_wfrag(H.ptr(x), H.dt(x), row_stride(x), H.ptr(w_packed), H.dt(w_packed), H.ptr(frag), H.ptr(bias),
+                                    H.ptr(out), H.dt(out), ldy, H.ptr(relu_gate),
                                     H.dt(relu_gate) if relu_gate is not None else 0,
                                     H.ptr(mask_lengths), H.ptr(skip_lengths), B, N, Cin, Cout, taps, flags, H.stream()))
     return out
