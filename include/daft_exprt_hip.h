@@ -1154,6 +1154,40 @@ int dx_vocoder_snake(const float* x, long ldx, const float* alpha, const float* 
 int dx_vocoder_post_clamp(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, const int64_t* n_rows,
                           int B, int N, int C, int taps, float in_slope, void* stream);
 
+/* ---- K35: the backward of K34 -- what fine-tuning a BigVGAN generator adds to K33.  Additive entry points (the ABI version stays).
+ * Layout and notation are dx_vocoder_snake's: x, dy, dx (B, N, C) time-major fp32, rows ld* floats apart, n_rows (B) int64, alpha and
+ * inv_beta (C) fp32 on the device in their final form, filters a HOST pointer to f_up[12] then f_down[12].
+ *
+ * dx_vocoder_snake_bwd: nothing is saved by the forward.  Per utterance b with n = n_rows[b] live rows and per channel c:
+ *     u[t]   = 2 * sum_i f_up[t + 15 - 2 i] * x[clamp(i - 5, 0, n - 1)]                  t in [0, 2 n)   (recomputed, as in the forward)
+ *     ds[t]  = sum_{m in [0, n), k in [0, 12) : clamp(2 m + k - 5, 0, 2 n - 1) = t} f_down[k] * dy[m]
+ *     w[t]   = 2 * alpha[c] * u[t]
+ *     du[t]  = ds[t] * (1 + inv_beta[c] * alpha[c] * sin(w[t]))
+ *     dx[j]  = 2 * sum_{t in [0, 2 n), i : clamp(i - 5, 0, n - 1) = j, 0 <= t + 15 - 2 i < 12} f_up[t + 15 - 2 i] * du[t]
+ *     dalpha[c]    = sum_b sum_t ds[t] * inv_beta[c] * u[t] * sin(w[t])
+ *     dinv_beta[c] = sum_b sum_t ds[t] * (1 - cos(w[t])) / 2
+ * The forward's first clamp replicates x's edge row, so dx[0] and dx[n - 1] also collect the five virtual rows on their side; its second
+ * clamp replicates s's edge value, so ds[0] and ds[2 n - 1] also collect the samples t in [-5, -1] and [2 n, 2 n + 4]; dy outside
+ * [0, n) counts as zero (it is not replicated); at n = 1 everything folds onto one row.  One accurate sincosf per sample, fp32 throughout.
+ *   x and dy rows >= n_rows[b] are NEVER READ; dx rows n_rows[b] .. N are written as zeros; dx aliases neither input.
+ *   Every dx[j] is one chain of fmas in one lane whose order depends on the row (and, at the two edge rows, on n) alone: an utterance gets
+ *   the same bits alone, in any batch, at any N and at any tile height.  x and dy are read once, dx written once; u, ds, du stay in registers.
+ *   tile_rows  rows per thread: 0 = the launcher's choice, otherwise one of dx_vocoder_snake_bwd_tile_rows(0), (1), ... (ascending; 0
+ *              past the end).  The rule for 0: the LARGEST supported height at which B * ceil(N / height) * C / 4 threads are still
+ *              >= 65536 (one wave on every SIMD of the 256 CUs), and the smallest height when none is.
+ *   dalpha, dinv_beta  (C) fp32, both given or both null (null: the sums and the second launch are skipped; ws may be null then).
+ *              No atomics: a thread sums, in double, the terms of the samples its tile owns (t in [2 m0, 2 m0 + 2 tile_rows)), writes one
+ *              partial per (utterance, tile, channel) to ws, and a second launch adds the partials in index order in double and rounds
+ *              once: two calls give the same bits.
+ *   ws         dx_vocoder_snake_bwd_workspace(B, N, C) bytes (0 for B = 0), 16-byte aligned; nothing in it has to be initialised.
+ * x, dy, dx, alpha, inv_beta 16-byte aligned; C and the leading dimensions multiples of 4 (DX_ERR_UNSUPPORTED otherwise), an unsupported
+ * tile_rows and more workgroups than grid.x holds likewise -- all before any launch. */
+int dx_vocoder_snake_bwd_tile_rows(int index);
+long dx_vocoder_snake_bwd_workspace(int B, int N, int C);
+int dx_vocoder_snake_bwd(const float* x, long ldx, const float* dy, long lddy, const float* alpha, const float* inv_beta,
+                         const float* filters, float* dx, long lddx, float* dalpha, float* dinv_beta, void* ws, const int64_t* n_rows,
+                         int B, int N, int C, int tile_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

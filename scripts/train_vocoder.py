@@ -1,21 +1,22 @@
 #!/usr/bin/env python
-"""Fine-tune a HiFi-GAN vocoder on the fine-tuning data set, on the GPU
+"""Fine-tune a HiFi-GAN or BigVGAN vocoder on the fine-tuning data set, on the GPU
     python scripts/train_vocoder.py -ft FINE_TUNING_DATASET -cfg CONFIG_JSON -g G_CKPT [-do DO_CKPT] -o OUT_DIR [--steps 1000]
                                     [--batch_size 16] [--segment_size 8192] [--compute_dtype fp32] [--checkpoint_interval 500]
                                     [--seed 1234]
 
   -ft    the `fine_tuning_dataset` directory `daft_exprt/fine_tune.py` writes: `<speaker>/<file>.npy` (teacher-forced mel) and
          `<speaker>/<file>.wav` (the cropped recording) per utterance
-  -cfg   HiFi-GAN's `config.json` of the pretrained generator (V1 and V3 qualify: every stage a multiple of 32 channels)
+  -cfg   the `config.json` of the pretrained generator: HiFi-GAN's (V1 and V3 qualify: every stage a multiple of 32 channels) or, with
+         an `activation` key, BigVGAN's (the 512-channel base models qualify, the 1536-channel models' 48- / 24-channel tail does not)
   -g     the pretrained generator checkpoint `g_XXXXXXXX`
-  -do    the discriminator / optimiser checkpoint `do_XXXXXXXX` to continue from; without it the discriminators start from their
-         initialisation
+  -do    the discriminator / optimiser checkpoint `do_XXXXXXXX` of THIS script to continue from; without it the discriminators
+         (multi-period and multi-scale for either family: an upstream BigVGAN `do_` file is not read) start from their initialisation
   -o     directory the checkpoints `g_%08d` / `do_%08d`, a copy of `config.json` and `vocoder_report.json` are written to;
          `scripts/synthesize.py -voc OUT_DIR/g_%08d` reads the result
 
 The generator trains on the kernels it is run with (`daft_exprt/vocoder_train.py`); the discriminators and the losses are plain torch.
 `vocoder_report.json` holds the utterances used / skipped / held out, per logged step the four loss terms and the held-out mel L1,
-that L1 for the starting and the final generator, and the steps per second.  The quality of a vocoder fine-tuned this way on real
+that L1 for the starting and the final generator, the generator's family and the steps per second.  The quality of a vocoder fine-tuned this way on real
 speech has not been measured, and neither has the exchange of `do_` files with HiFi-GAN's own code."""
 import argparse
 import json
@@ -58,11 +59,11 @@ def check_args(args):
         raise SystemExit(f'train_vocoder.py: --steps {args.steps}, --batch_size {args.batch_size}, --segment_size {args.segment_size} '
                          f'and --checkpoint_interval {args.checkpoint_interval} must be at least 1')
     from daft_exprt import vocoder as V
-    from daft_exprt.vocoder_train import LossMel, trainable_stages
+    from daft_exprt.vocoder_train import LossMel, trainable_config
     try:
         config = V.load_config(args.config)
         V.validate_config(config)
-        trainable_stages(config)
+        trainable_config(config)
         LossMel(config)
     except (ValueError, json.JSONDecodeError) as e:
         raise SystemExit(f'train_vocoder.py: {args.config}: {e}')

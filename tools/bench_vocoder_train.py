@@ -8,7 +8,13 @@ launch, the discriminators (forward + backward, with the backward of the losses 
 the losses and the optimisers (events around each piece: kernel time plus its launch gaps), `dx_vocoder_wgrad`'s TFLOP/s per input
 channel width -- and, as yardstick, the same generator's forward + backward through `F.conv1d` / `F.conv_transpose1d` autograd on
 the same device, weights and segment.  The yardstick lives here only: it is no path of the package.
-Run:  python tools/bench_vocoder_train.py [--reps 5] [--batch 16] [--segment 8192]
+
+`--bigvgan` adds, under "bigvgan", a BigVGAN generator of the base layout (V1's shapes with `snakebeta` activations in log scale,
+weights from a seed) on the same batch and segment: its forward + backward ms in both operand types, and per stage the activation's
+forward (`dx_vocoder_snake`) and backward (`dx_vocoder_snake_bwd`, with its reduce launch) alone, 20 launches per timed window -- ms, bytes (forward: x read and y
+written; backward: x and dy read, dx written), TB/s, the rate against a float copy of the same bytes timed in the same run, the
+tile height the backward's launcher chose -- and both launches' share of the generator's forward + backward.
+Run:  python tools/bench_vocoder_train.py [--reps 5] [--batch 16] [--segment 8192] [--bigvgan]
 """
 import argparse
 import json
@@ -166,11 +172,96 @@ def instrumented_step(VT, generator, mpd, msd, optim_g, optim_d, loss_mel, mel, 
     return whole, share, rate
 
 
+LAUNCHES = 20
+
+
+def launcher_tile_rows(H, B, N, C):
+    ''' the height `dx_vocoder_snake_bwd` picks for tile_rows = 0, by the rule the header states: the largest supported height that
+        still gives 65536 threads, else the smallest '''
+    heights, i = [], 0
+    while H.lib().dx_vocoder_snake_bwd_tile_rows(i) > 0:
+        heights.append(H.lib().dx_vocoder_snake_bwd_tile_rows(i))
+        i += 1
+    fits = [h for h in heights if B * -(-N // h) * (C // 4) >= 65536]
+    return max(fits) if fits else min(heights)
+
+
+def bigvgan(args, base_cfg, mel, proj, lengths, dev):
+    ''' the "bigvgan" entry of the result '''
+    import ctypes
+    from daft_exprt import _hip as H
+    from daft_exprt import bigvgan_train as BT
+    from daft_exprt import vocoder_train as VT
+    from tests import bigvgan_oracle as BO
+    from tests import vocoder_oracle as O
+    cfg = dict(base_cfg, activation='snakebeta', snake_logscale=True)
+    seed_mel = O.make_mel(cfg, (12,), seed=0)
+    weights, raw, _, filters = BO.make_weights(cfg, seed_mel, (12,), seed=0)
+    sd = BO.state_dict(cfg, weights, raw, filters, form='weight_norm')
+    out = {'config': 'V1 + snakebeta (log scale)', 'activations': len(BO.fed_convs(cfg))}
+    for dtype in ('fp32', 'bf16'):
+        generator = VT.trainable_generator(cfg, sd, compute_dtype=dtype).to(dev)
+
+        def gen_fwd_bwd():
+            for p in generator.parameters():
+                p.grad = None
+            (generator(mel, lengths) * proj).sum().backward()
+        for _ in range(2):
+            gen_fwd_bwd()
+        torch.cuda.synchronize()
+        out[dtype] = {'generator_forward_backward_ms': _timed(gen_fwd_bwd, args.reps)}
+        del generator
+        torch.cuda.empty_cache()
+    # the activation alone, per stage: rows and channels of the stage, as many launches per step as the stage has activations
+    g = torch.Generator().manual_seed(2)
+    taps = (ctypes.c_float * 24)(*filters[0].tolist(), *filters[1].tolist())
+    nk, rows, c = len(cfg['resblock_kernel_sizes']), args.segment // cfg['hop_size'], cfg['upsample_initial_channel']
+    per_block = sum(2 * len(d) for d in cfg['resblock_dilation_sizes'])
+    stages, fwd_total, bwd_total = [], 0., 0.
+    for i, u in enumerate(cfg['upsample_rates']):
+        rows, c = rows * u, c // 2
+        last = i == len(cfg['upsample_rates']) - 1
+        count = per_block + (1 if last else 0)                          # activation_post runs at the last stage's shape
+        x, dy = (torch.randn((args.batch, rows, c), generator=g).to(dev) for _ in range(2))
+        alpha, inv_beta = (t.to(dev) for t in BO.final_params(0.5 * torch.randn((c,), generator=g), 0.5 * torch.randn((c,), generator=g), True))
+        n = torch.full((args.batch,), rows, dtype=torch.int64, device=dev)
+        y = torch.empty_like(x)
+        fwd = lambda: H.check(H.lib().dx_vocoder_snake(H.ptr(x), c, H.ptr(alpha), H.ptr(inv_beta), ctypes.addressof(taps), H.ptr(y), c,      # noqa: E731
+                                                       H.ptr(n), args.batch, rows, c, H.stream()))
+        bwd = lambda: BT.snake_backward(x, dy, alpha, inv_beta, taps, n)      # noqa: E731
+        el = args.batch * rows * c
+        entry = {'stage': i, 'rows': rows, 'channels': c, 'launches_per_step': count,
+                 'backward_tile_rows': launcher_tile_rows(H, args.batch, rows, c), 'forward_tile_rows': H.lib().dx_vocoder_snake_tile_rows()}
+        for name, fn, n_bytes in (('forward', fwd, 8 * el), ('backward', bwd, 12 * el)):
+            src = torch.empty(n_bytes // 8, dtype=torch.float32, device=dev).normal_()
+            dst = torch.empty_like(src)
+            copy = lambda: dst.copy_(src)      # noqa: E731
+            for f in (fn, copy):
+                f()
+                f()
+            torch.cuda.synchronize()
+            # LAUNCHES calls per timed window: one launch of 0.1 ms between two events is as much the events as the kernel
+            ms, copy_ms = (_timed(lambda f=f: [f() for _ in range(LAUNCHES)], args.reps) / LAUNCHES for f in (fn, copy))
+            entry[name] = {'ms': ms, 'bytes': n_bytes, 'tbps': n_bytes / (ms * 1e-3) / 1e12, 'copy_ms': copy_ms,
+                           'rate_over_copy': copy_ms / ms}
+            del src, dst
+        fwd_total += count * entry['forward']['ms']
+        bwd_total += count * entry['backward']['ms']
+        stages.append(entry)
+    out['snake_stages'] = stages
+    out['snake_forward_ms_per_step'], out['snake_backward_ms_per_step'] = fwd_total, bwd_total
+    for dtype in ('fp32', 'bf16'):
+        whole = out[dtype]['generator_forward_backward_ms']
+        out[dtype]['snake_forward_share'], out[dtype]['snake_backward_share'] = fwd_total / whole, bwd_total / whole
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--segment', type=int, default=8192)
+    ap.add_argument('--bigvgan', action='store_true', help='also measure a BigVGAN generator of the base layout (V1 + snakebeta)')
     args = ap.parse_args()
     warnings.simplefilter('ignore')
     from daft_exprt import vocoder_train as VT
@@ -221,6 +312,10 @@ def main():
         torch_fwd_bwd()
     torch.cuda.synchronize()
     out['torch_conv1d_generator_forward_backward_ms'] = _timed(torch_fwd_bwd, args.reps)
+    if args.bigvgan:
+        del tw
+        torch.cuda.empty_cache()
+        out['bigvgan'] = bigvgan(args, cfg, mel, proj, lengths, dev)
     print(json.dumps(out))
 
 

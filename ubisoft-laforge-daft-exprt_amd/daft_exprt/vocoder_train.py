@@ -1,5 +1,7 @@
 """Fine-tuning of the HiFi-GAN vocoder (Kong et al. 2020) on the GPU: from a `fine_tune` data set and a pretrained `g_` / `do_`
-pair to the `g_XXXXXXXX` file `Vocoder.from_checkpoint` reads.
+pair to the `g_XXXXXXXX` file `Vocoder.from_checkpoint` reads.  A BigVGAN generator (a config with an `activation`) trains through
+`daft_exprt/bigvgan_train.py`, which adds the activation's backward (K35) to what is here; `trainable_generator` picks the class, and
+the discriminators, losses, sampler, checkpoints and `fine_tune_vocoder` below serve both families.
 
 The generator trains on the kernels it is run with (`daft_exprt/vocoder.py`, K24), under their numerical contract -- dead rows past
 each utterance, bf16 or fp32 operands, fp32 accumulation:
@@ -268,19 +270,45 @@ class _ConvList(nn.Module):
             setattr(self, name, nn.ModuleList(layers))
 
 
-def trainable_stages(cfg):
+def _stage_channels(cfg, hint):
     ''' raises ValueError naming the first layer whose channel counts the MFMA kernels do not take (multiples of 32; conv_pre's
-        mel bins are zero-padded, conv_post's single output is torch), or the `activation` of a BigVGAN config: its anti-aliased
-        activation has a forward kernel only (inference: `vocoder.Vocoder`) '''
-    if cfg.get('activation') is not None:
-        raise ValueError(f'vocoder training: the config\'s "activation" is {cfg["activation"]!r}: fine-tuning covers HiFi-GAN generators '
-                         f'only, a BigVGAN generator can be loaded for inference (daft_exprt.vocoder.Vocoder) but not trained')
+        mel bins are zero-padded, conv_post's single output is torch) '''
     for name, kind, shape, _ in V.layer_table(cfg):
         cin, cout = (shape[0], shape[1]) if kind == 'up' else (shape[1], shape[0])
         bad = [c for c, skip in ((cin, name == 'conv_pre'), (cout, name == 'conv_post')) if not skip and c % 32]
         if bad:
-            raise ValueError(f'vocoder training: layer "{name}" has {bad[0]} channels; every stage must be a multiple of 32 '
-                             f'(HiFi-GAN V1 and V3 qualify, V2\'s 16- / 8-channel tail does not)')
+            raise ValueError(f'vocoder training: layer "{name}" has {bad[0]} channels; every stage must be a multiple of 32 ({hint})')
+
+
+def trainable_stages(cfg):
+    ''' what `TrainableGenerator` takes: raises ValueError naming the first layer whose channel counts are no multiples of 32, or the
+        `activation` of a BigVGAN config -- that generator trains through `bigvgan_train.TrainableBigVGAN` (`trainable_generator`
+        picks the class, `trainable_config` the check) '''
+    if cfg.get('activation') is not None:
+        raise ValueError(f'vocoder training: the config\'s "activation" is {cfg["activation"]!r}: TrainableGenerator covers HiFi-GAN '
+                         f'generators only; a BigVGAN generator trains through daft_exprt.bigvgan_train.TrainableBigVGAN '
+                         f'(vocoder_train.trainable_generator returns the right class)')
+    _stage_channels(cfg, 'HiFi-GAN V1 and V3 qualify, V2\'s 16- / 8-channel tail does not')
+
+
+def trainable_config(cfg):
+    ''' the stage check of the class `trainable_generator` would build; returns the family, "bigvgan" or "hifi-gan" '''
+    if V.is_bigvgan(cfg):
+        from daft_exprt.bigvgan_train import bigvgan_stages
+        bigvgan_stages(cfg)
+        return 'bigvgan'
+    trainable_stages(cfg)
+    return 'hifi-gan'
+
+
+def trainable_generator(config, state_dict, compute_dtype='fp32'):
+    ''' `TrainableGenerator` for a HiFi-GAN config, `bigvgan_train.TrainableBigVGAN` for one with an `activation` '''
+    cfg = V.load_config(config)
+    V.validate_config(cfg)
+    if V.is_bigvgan(cfg):
+        from daft_exprt.bigvgan_train import TrainableBigVGAN
+        return TrainableBigVGAN(cfg, state_dict, compute_dtype=compute_dtype)
+    return TrainableGenerator(cfg, state_dict, compute_dtype=compute_dtype)
 
 
 class TrainableGenerator(nn.Module):
@@ -293,7 +321,7 @@ class TrainableGenerator(nn.Module):
         V.validate_config(self.config)
         if compute_dtype not in _TDT:
             raise ValueError(f'compute_dtype is {compute_dtype!r}, expected "bf16" or "fp32"')
-        trainable_stages(self.config)
+        self._check_stages()
         cfg = self.config
         self.compute_dtype = compute_dtype
         self.rates = [int(u) for u in cfg['upsample_rates']]
@@ -302,7 +330,7 @@ class TrainableGenerator(nn.Module):
         self.num_mels, self.hop = int(cfg['num_mels']), int(cfg['hop_size'])
         self.mel_channels = -(-self.num_mels // 32) * 32
         folded = V.folded_state(cfg, state_dict)                     # (the biases, and every shape check of the inference path)
-        layer = lambda name: self._layer(state_dict, name, folded[name][1])      # noqa: E731
+        layer = lambda name: self._layer(state_dict, self._source_name(state_dict, name), folded[name][1])      # noqa: E731
         self.conv_pre = layer('conv_pre')
         self.ups = nn.ModuleList(layer(f'ups.{i}') for i in range(len(self.rates)))
         nk = len(self.res_dilations)
@@ -315,6 +343,14 @@ class TrainableGenerator(nn.Module):
         self.resblocks = nn.ModuleList(blocks)
         self.conv_post = layer('conv_post')
 
+    def _check_stages(self):
+        trainable_stages(self.config)
+
+    @staticmethod
+    def _source_name(state_dict, name):
+        ''' the layer's prefix in the state dict '''
+        return name
+
     @staticmethod
     def _layer(state_dict, name, bias):
         ''' g and v as the checkpoint holds them (so a fine-tuned file continues the pretrained parametrisation), or g = ||w||, v = w '''
@@ -326,9 +362,18 @@ class TrainableGenerator(nn.Module):
                     mod.weight_v.copy_(state_dict[f'{name}{v_key}'].detach().float())
         return mod
 
-    def _conv(self, name, x, n, dilation, slope=V.LRELU_SLOPE):
+    _slope = V.LRELU_SLOPE      # of the leaky-ReLU the convs apply to their input (a BigVGAN generator: 1, `_fed` is its activation)
+
+    def _conv(self, name, x, n, dilation, slope=None):
         mod = self.get_submodule(name)
-        return _Conv.apply(x, mod.weight(), mod.bias, n, dilation, slope, self.compute_dtype)
+        return _Conv.apply(x, mod.weight(), mod.bias, n, dilation, self._slope if slope is None else slope, self.compute_dtype)
+
+    def _fed(self, name, x, n):
+        ''' what the conv `name` reads: x itself (the leaky-ReLU is applied as the conv stages its input) '''
+        return x
+
+    def _post(self, x, n):
+        return _Post.apply(x, self.conv_post.weight(), self.conv_post.bias, n)
 
     def forward(self, mel, lengths):
         ''' mel (B, num_mels, T) natural-log mel on the device (columns at or past `lengths` are not read), lengths (B,) int64
@@ -348,20 +393,20 @@ class TrainableGenerator(nn.Module):
             nk = len(self.res_dilations)
             for i, u in enumerate(self.rates):
                 up = self.ups[i]
-                x = _Upsample.apply(x, up.weight(), up.bias, n, u, V.LRELU_SLOPE, self.compute_dtype)
+                x = _Upsample.apply(x, up.weight(), up.bias, n, u, self._slope, self.compute_dtype)
                 n = n * u
                 total = None
                 for j, dils in enumerate(self.res_dilations):
                     r, block = x, f'resblocks.{i * nk + j}'
                     for m, d in enumerate(dils):
                         if self.resblock == '1':
-                            t = self._conv(f'{block}.convs1.{m}', r, n, d)
-                            r = r + self._conv(f'{block}.convs2.{m}', t, n, 1)
+                            t = self._conv(f'{block}.convs1.{m}', self._fed(f'{block}.convs1.{m}', r, n), n, d)
+                            r = r + self._conv(f'{block}.convs2.{m}', self._fed(f'{block}.convs2.{m}', t, n), n, 1)
                         else:
-                            r = r + self._conv(f'{block}.convs.{m}', r, n, d)
+                            r = r + self._conv(f'{block}.convs.{m}', self._fed(f'{block}.convs.{m}', r, n), n, d)
                     total = r if total is None else total + r
                 x = total / nk
-            return _Post.apply(x, self.conv_post.weight(), self.conv_post.bias, n)
+            return self._post(self._fed('conv_post', x, n), n)
 
 
 # ---- discriminators (Kong et al. 2020, sections 2.2 - 2.3), plain torch -------------------------------------------------------------
@@ -691,7 +736,7 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
         raise ValueError(f'{g_checkpoint}: no "generator" entry (expected a HiFi-GAN generator checkpoint)')
     torch.manual_seed(seed)
     loss_mel = LossMel(config).to(device)
-    generator = TrainableGenerator(config, ckpt['generator'], compute_dtype=compute_dtype).to(device)
+    generator = trainable_generator(config, ckpt['generator'], compute_dtype=compute_dtype).to(device)
     mpd, msd = MultiPeriodDiscriminator().to(device), MultiScaleDiscriminator().to(device)
     optim_g = torch.optim.AdamW(generator.parameters(), LEARNING_RATE, betas=ADAM_BETAS)
     optim_d = torch.optim.AdamW(list(msd.parameters()) + list(mpd.parameters()), LEARNING_RATE, betas=ADAM_BETAS)
@@ -705,7 +750,8 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
     sched_g = torch.optim.lr_scheduler.ExponentialLR(optim_g, gamma=LR_DECAY)
     sched_d = torch.optim.lr_scheduler.ExponentialLR(optim_d, gamma=LR_DECAY)
     report = {'utterances_used': len(train), 'utterances_skipped': skipped, 'utterances_held_out': len(held_out),
-              'compute_dtype': compute_dtype, 'batch_size': batch_size, 'segment_size': segment_size, 'first_step': first_step, 'log': []}
+              'generator_family': 'bigvgan' if V.is_bigvgan(config) else 'hifi-gan', 'compute_dtype': compute_dtype,
+              'batch_size': batch_size, 'segment_size': segment_size, 'first_step': first_step, 'log': []}
     validate = lambda: held_out_mel_l1(config, generator.state_dict(), held_out, compute_dtype, device, centered)   # noqa: E731
     report['held_out_mel_l1_start'] = validate()
     step, epoch, last_val = first_step, max(sampler.epoch, 1), report['held_out_mel_l1_start']
