@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Micro-benchmarks of individual HIP kernels on the GPU box (development aid).
-usage: python tools/bench_ops.py conv"""
+usage: python tools/bench_ops.py conv | wgrad | ln | convln | attn | mel | lnbwd | gu"""
 import os
 import sys
 
@@ -198,3 +198,67 @@ def bench_lnbwd():
 if __name__ == '__main__' and len(sys.argv) > 1 and sys.argv[1] == 'lnbwd':
     bench_lnbwd()
 
+
+
+def bench_gu():
+    ''' the five launches of the Gaussian upsampler alone, on the lengths and durations of the bench batch: median us per launch over
+        GU_ITERS calls, each timed with its own pair of HIP events after a warm-up '''
+    import math
+    from daft_exprt import data_loader
+    from daft_exprt.hparams import HyperParams
+    hp = HyperParams(verbose=False, training_files='none', validation_files='none', output_directory='/nonexistent', language='english',
+                     speakers=['a', 'b'])
+    dev = torch.device('cuda:0')
+    B = int(os.environ.get('GU_B', '48'))
+    cb = data_loader.synthetic_batch(hp, B, seed=1234, t_min=1, t_max=1000, force_first_full=True)
+    dur_f, dur_i, energy, pitch, in_len, out_len = (cb[i].to(dev) for i in (1, 2, 3, 4, 5, 9))
+    L, T, C = dur_i.shape[1], int(cb[8].shape[2]), 128
+    g = torch.Generator().manual_seed(0)
+    rnd = lambda *shape: torch.randn(*shape, generator=g).to(dev)
+    uni = lambda fan_in, *shape: ((torch.rand(*shape, generator=g) * 2 - 1) / math.sqrt(fan_in)).to(dev)     # torch's default init
+    enc = rnd(B, L, C) * (torch.arange(L, device=dev)[None, :, None] < in_len[:, None, None])
+    P = {}
+    for name in ('dur', 'en', 'pi'):
+        P['w_' + name], P['b_' + name] = uni(3, C, 1, 3), uni(3, C)
+    P['w_range'], P['b_range'] = uni(C, 1, C), uni(C, 1)
+    pos, gout = rnd(T, C), rnd(B, T, C)
+    xp, ranges, r_pre, _ = ops.gu_prepare(enc, dur_f, energy, pitch, in_len, P, save=True)
+    means, _ = ops.gu_means(dur_i)
+    _, weights = ops.gu_upsample_fwd(xp, ranges, means, in_len, T, out_len, pos)
+    H, lib = ops.H, ops.H.lib()
+    dw, dsum = torch.empty(B, L, T, device=dev), torch.empty(B, T, device=dev)
+    dxp, drin, dr = torch.empty_like(xp), torch.empty_like(xp), torch.empty(B, L, device=dev)
+    out = torch.empty(B, T, C, device=dev)
+    calls = {
+        'prepare': lambda: ops.gu_prepare(enc, dur_f, energy, pitch, in_len, P, save=True),
+        'means': lambda: ops.gu_means(dur_i),
+        'fwd': lambda: H.check(lib.dx_gu_upsample_fwd(H.ptr(xp), H.ptr(ranges), H.ptr(means), H.ptr(in_len), H.ptr(out_len), H.ptr(pos),
+                                                      H.ptr(weights), H.ptr(out), B, L, T, C, H.stream())),
+        'bwd1+bwd2': lambda: H.check(lib.dx_gu_upsample_bwd(H.ptr(gout), H.ptr(xp), H.ptr(weights), H.ptr(means), H.ptr(ranges), H.ptr(r_pre),
+                                                            H.ptr(P['w_range']), H.ptr(in_len), H.ptr(out_len), H.ptr(dw), H.ptr(dsum),
+                                                            H.ptr(dxp), H.ptr(drin), H.ptr(dr), B, L, T, C, H.stream())),
+    }
+    iters = int(os.environ.get('GU_ITERS', '50'))
+    frames, phon = int(out_len.sum()), int(in_len.sum())
+    print(f'gu B={B} L={L} T={T}: {phon} phonemes, {frames} valid frames | lib {os.environ.get("DX_HIP_LIB", "default")}')
+    total = 0.
+    for name, fn in calls.items():
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(iters):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            e.synchronize()
+            us.append(s.elapsed_time(e) * 1e3)
+        us.sort()
+        total += us[len(us) // 2]
+        print(f'  {name:10s} median {us[len(us) // 2]:7.1f} us   min {us[0]:7.1f}   max {us[-1]:7.1f}')
+    print(f'  sum of medians {total:7.1f} us (event pairs include the launch gap; bwd1 and bwd2 are one entry point, two launches)')
+
+
+if __name__ == '__main__' and len(sys.argv) > 1 and sys.argv[1] == 'gu':
+    bench_gu()

@@ -9,9 +9,11 @@
 //   x_up[t] = sum_l w[l,t] x'_l                                                      (model.py:659)
 //
 // The reference materialises a (B, L, 128, T) product (3.4 GB at B=48); here a workgroup owns 32 frames of one
-// utterance, keeps the (L-chunk x 32) weight tile in LDS and contracts it against x' from L2 -- only w (B,L,T)
-// (it is a model output, "alignments") and x_up ever reach HBM.  The kernel also applies the decoder's
-// positional add + mask (model.py:696-701) so the decoder input is produced in the same pass.
+// utterance, keeps the weights of the phonemes that reach those frames in LDS and contracts them against x' from
+// L2 -- only w (B,L,T) (it is a model output, "alignments") and x_up ever reach HBM.  The kernel also applies the
+// decoder's positional add + mask (model.py:696-701) so the decoder input is produced in the same pass.
+// Forward and backward are banded: a Gaussian is exactly 0.f outside its phoneme's reach (gu_reach), so each
+// 32-frame tile works on a compacted list of the phonemes that reach it and each phoneme on its own frames.
 #include "dx_common.h"
 
 namespace {
@@ -77,6 +79,64 @@ __global__ __launch_bounds__(64) void gu_means_kernel(const int64_t* __restrict_
   if (lane == 0) totals[b] = carry;
 }
 
+// ---------------------------------------------------------------- the reach of a phoneme
+// p[l,t] = expf(a), a = -(t + .5 - mu)^2 / (2 sd^2) - logf(sd) - LOG_SQRT_2PI, is exactly 0.f wherever a is below expf's underflow
+// point.  The smallest fp32 denormal is 2^-149 and anything under 2^-150 = e^-103.97 rounds to 0, so a device expf that keeps
+// denormals returns 0 for a < -103.98; one that flushes them returns 0 already below -87.4, which only makes the zero region larger.
+// With q = (t + .5 - mu)^2 / (2 sd^2):  q > GU_QZERO - logf(sd)  gives  a < -GU_QZERO - 0.9189 = -106.9, three units under the
+// underflow point -- the few ulp of the divide, of logf and of expf's own argument reduction are < 1e-4 of that margin (for a huge q
+// the absolute rounding grows with q, but so does the distance).  -logf(sd) > 0 for sd < 1 widens the reach, logf(sd) > 0 narrows
+// it; the max with 0 only matters for sd > e^106, which fp32 does not hold.  So p can be non-zero only on the frames
+//     |t + .5 - mu| <= sd sqrt(2 (GU_QZERO - logf(sd)))  =: r
+// and [lo, hi] = [floor(mu - .5 - r'), ceil(mu - .5 + r')] with r' = 1.001 r + 1 (a frame of slack over the roundings of sqrtf, of
+// the products and of mu - .5 -/+ r') contains them all.  sd that is 0, negative, infinite or NaN (and a mean that is not a
+// sensible number) gives the whole axis: when in doubt, evaluate.  Forward and backward call this one function, so they agree on
+// the band; inside it every pair is evaluated with the expression above, outside it the value is the constant 0.f.
+constexpr float GU_QZERO = 106.f;
+__device__ __forceinline__ void gu_reach(float mu, float sd, float logsd, int& lo, int& hi) {
+  const float r = sd * sqrtf(2.f * fmaxf(GU_QZERO - logsd, 0.f)) * 1.001f + 1.f;
+  const float c = mu - 0.5f;
+  if (sd > 0.f && r < 1e9f && fabsf(c) < 1e9f) {   // |c -/+ r| < 2e9 < 2^31
+    lo = (int)floorf(c - r);
+    hi = (int)ceilf(c + r);
+  } else {
+    lo = -2147483647 - 1;
+    hi = 2147483647;
+  }
+}
+
+constexpr int TT = 32;      // frames per workgroup
+constexpr int GU_R = 256;   // phonemes examined per round: one per thread of the workgroup
+constexpr int GU_CAP = 128; // (phoneme, 32 frames) rows of Gaussian values a forward workgroup keeps in LDS; later ones go through `weights`
+
+// One round's compacted list: the phonemes of [l0, l0 + GU_R) below `len` whose reach touches frames [t0, t1], in ascending l, with
+// their per-phoneme invariants (2 sd^2 and logf(sd): the same values and roundings the per-pair expression used to recompute).
+struct GuList {
+  int l[GU_R];
+  float mu[GU_R], h[GU_R], logsd[GU_R];
+  int in[GU_R];     // in[i] != 0: phoneme l0 + i is on the list
+  int part[4];
+};
+// Every thread of the 256-thread workgroup must call it; returns the list's length (<= GU_R: one slot per thread, so no index can
+// pass the arrays).  Ends with a barrier; the caller puts another one between its last read of `s` and the next call.
+__device__ __forceinline__ int gu_compact(GuList& s, const float* __restrict__ mu, const float* __restrict__ sg, int l0, int len, int t0, int t1) {
+  const int tid = threadIdx.x, l = l0 + tid;
+  int in = 0;
+  float m = 0.f, sd = 1.f, lsd = 0.f;
+  if (l < len) {
+    m = mu[l]; sd = sg[l]; lsd = logf(sd);
+    int lo, hi;
+    gu_reach(m, sd, lsd, lo, hi);
+    in = (lo <= t1 && hi >= t0) ? 1 : 0;
+  }
+  s.in[tid] = in;
+  int n = 0;
+  const int pos = dx_block_scan_step<4>(in, n, s.part);   // exclusive: pos <= tid < GU_R
+  if (in) { s.l[pos] = l; s.mu[pos] = m; s.h[pos] = 2.f * sd * sd; s.logsd[pos] = lsd; }
+  __syncthreads();
+  return n;
+}
+
 // ---------------------------------------------------------------- upsample forward
 struct UpArgs {
   const float* xp; const float* ranges; const float* means; const int64_t* in_len; const int64_t* out_len;
@@ -85,34 +145,50 @@ struct UpArgs {
   float* out;         // (B, T, D): (x_up + pos) masked by out_len when pos != null, else raw x_up
   int L, T;
 };
-constexpr int TT = 32;   // frames per workgroup
-constexpr int LC = 64;   // phoneme rows per LDS chunk
 
-__global__ __launch_bounds__(256) void gu_upsample_fwd_kernel(UpArgs a) {
-  __shared__ float Wt[LC][TT + 1];
+// A workgroup owns 32 frames of one utterance.  Pass 1 walks the phonemes in rounds of GU_R: compact the ones that reach the tile,
+// evaluate each (phoneme, frame) pair of the list ONCE (the value stays in LDS row `slot`, or, past GU_CAP rows, in its own element
+// of `weights`, which the same thread reads back) and add it to the frame's partial sum.  Pass 2 divides by the denominators,
+// contracts the weights against x' and only then stores: the decoder input, the listed weights and 0 for every other row of the
+// tile.  All loads come before all stores because a wave's loads and stores share one in-order counter (vmcnt): a load issued
+// behind twenty stores waits for their acknowledgements from HBM.  Every skipped term is an exact 0, and the order of what is left
+// is the one the dense form had: partial sums by l mod 8 in ascending l, then k = 0..7; fmaf in ascending l.
+// Channels: thread (ft, cg) holds channels 32 v + 4 cg + i (v, i < 4), so that the eight threads of a frame read and write 128
+// contiguous bytes per instruction.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void gu_upsample_fwd_kernel(UpArgs a) {
+  __shared__ GuList ls;
+  __shared__ float Wt[GU_CAP][TT + 1];
   __shared__ float part[8][TT];
   __shared__ float denom[TT];
-  __shared__ int lrange[2];   // [first, last] phoneme whose Gaussian is not exactly zero on this 32-frame tile
   const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * TT;
-  if (tid == 0) { lrange[0] = 1 << 30; lrange[1] = -1; }
-  __syncthreads();
-  const int tt = tid & 31, lg = tid >> 5;          // phase 1/2: (frame, phoneme-group)
+  const int tt = tid & 31, lg = tid >> 5;          // pass 1 / normalisation / weight stores: (frame, l mod 8)
   const int L = a.L, T = a.T;
-  const int len = (int)a.in_len[b];
+  const int len = (int)dx_clamp_len(a.in_len, b, L);
+  const int t1 = min(t0 + TT, T) - 1;
+  const bool tin = t0 + tt < T;
   const float tc = (float)(t0 + tt) + 0.5f;
   const float* mu = a.means + (long)b * L;
   const float* sg = a.ranges + (long)b * L;
-  // phase 1: denominators
+  float* wcol = a.weights + (long)b * L * T + t0 + tt;   // + l * T; only dereferenced when tin
+  // pass 1
   float s = 0.f;
-  int lo = 1 << 30, hi = -1;
-  for (int l = lg; l < len; l += 8) {
-    const float sd = sg[l], dlt = tc - mu[l];
-    const float pv = expf(-(dlt * dlt) / (2.f * sd * sd) - logf(sd) - LOG_SQRT_2PI);
-    s += pv;
-    if (pv != 0.f) { lo = min(lo, l); hi = max(hi, l); }   // far-away Gaussians underflow to exactly 0 in fp32
+  int base = 0, n = 0;
+  for (int l0 = 0; l0 < len; l0 += GU_R) {
+    n = gu_compact(ls, mu, sg, l0, len, t0, t1);
+    for (int j = 0; j < n; ++j) {
+      const int l = ls.l[j];
+      if ((l & 7) == lg) {
+        const float dlt = tc - ls.mu[j];
+        const float pv = expf(-(dlt * dlt) / ls.h[j] - ls.logsd[j] - LOG_SQRT_2PI);
+        s += pv;
+        if (base + j < GU_CAP) Wt[base + j][tt] = pv;
+        else if (tin) wcol[(long)l * T] = pv;
+      }
+    }
+    base += n;
+    __syncthreads();
   }
   part[lg][tt] = s;
-  if (hi >= 0) { atomicMin(&lrange[0], lo); atomicMax(&lrange[1], hi); }
   __syncthreads();
   if (tid < TT) {
     float d = 0.f;
@@ -121,96 +197,117 @@ __global__ __launch_bounds__(256) void gu_upsample_fwd_kernel(UpArgs a) {
     denom[tid] = d + 1e-20f;
   }
   __syncthreads();
-  // phase 2: weights out + contraction against x'
-  const int ft = tid >> 3, cg = tid & 7;            // (frame, 16-channel group)
-  float acc[16];
+  // pass 2
+  const int ft = tid >> 3, cg = tid & 7;            // contraction: (frame, channel group)
+  f32x4 acc[4];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int v = 0; v < 4; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
   const float den = denom[tt];
-  for (int l0 = 0; l0 < L; l0 += LC) {
-    for (int l = l0 + lg; l < min(L, l0 + LC); l += 8) {
-      float w = 0.f;
-      if (l < len) {
-        const float sd = sg[l], dlt = tc - mu[l];
-        w = expf(-(dlt * dlt) / (2.f * sd * sd) - logf(sd) - LOG_SQRT_2PI) / den;
+  const bool one_round = len <= GU_R;               // then `ls` still holds the only list
+  const bool valid = a.pos ? t0 + ft < (int)a.out_len[b] : true;
+  base = 0;
+  for (int l0 = 0; l0 < L; l0 += GU_R) {
+    const bool live = l0 < len;                     // a round with phonemes below len: it has a list
+    if (live) {
+      if (!one_round) n = gu_compact(ls, mu, sg, l0, len, t0, t1);
+      for (int j = 0; j < n; ++j) {
+        const int l = ls.l[j];
+        if ((l & 7) == lg) {
+          if (base + j < GU_CAP) Wt[base + j][tt] = Wt[base + j][tt] / den;
+          else if (tin) wcol[(long)l * T] = wcol[(long)l * T] / den;
+        }
       }
-      Wt[l - l0][tt] = w;
-      if (t0 + tt < T) a.weights[((long)b * L + l) * T + t0 + tt] = w;
-    }
-    __syncthreads();
-    // weights outside [lrange] are exactly zero on this tile: the contraction skips them (exact, ~10x less work)
-    const int lmax = min(min(min(L, l0 + LC), len), lrange[1] + 1);
-    for (int l = max(l0, lrange[0]); l < lmax; ++l) {
-      const float w = Wt[l - l0][ft];
-      const f32x4* xr = reinterpret_cast<const f32x4*>(a.xp + ((long)b * L + l) * D + cg * 16);
+      __syncthreads();
+#pragma unroll 2
+      for (int j = 0; j < n; ++j) {
+        const int l = ls.l[j];
+        float w;
+        if (base + j < GU_CAP) w = Wt[base + j][ft];
+        else w = t0 + ft < T ? a.weights[((long)b * L + l) * T + t0 + ft] : 0.f;   // written by this workgroup before the barrier
+        const f32x4* xr = reinterpret_cast<const f32x4*>(a.xp + ((long)b * L + l) * D) + cg;
 #pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const f32x4 x = xr[v];
-        acc[v * 4 + 0] = fmaf(w, x[0], acc[v * 4 + 0]); acc[v * 4 + 1] = fmaf(w, x[1], acc[v * 4 + 1]);
-        acc[v * 4 + 2] = fmaf(w, x[2], acc[v * 4 + 2]); acc[v * 4 + 3] = fmaf(w, x[3], acc[v * 4 + 3]);
+        for (int v = 0; v < 4; ++v) {
+          const f32x4 x = xr[v * 8];
+          acc[v][0] = fmaf(w, x[0], acc[v][0]); acc[v][1] = fmaf(w, x[1], acc[v][1]);
+          acc[v][2] = fmaf(w, x[2], acc[v][2]); acc[v][3] = fmaf(w, x[3], acc[v][3]);
+        }
       }
     }
-    __syncthreads();
-  }
-  const int t = t0 + ft;
-  if (t < T) {
-    float* o = a.out + ((long)b * T + t) * D + cg * 16;
-    if (a.pos) {
-      const bool valid = t < (int)a.out_len[b];
-      const float* pr = a.pos + (long)t * D + cg * 16;
+    if (l0 + GU_R >= L && t0 + ft < T) {            // after the last round's contraction: the decoder input
+      const int t = t0 + ft;
+      f32x4* o = reinterpret_cast<f32x4*>(a.out + ((long)b * T + t) * D) + cg;
+      if (a.pos) {
+        const f32x4* pr = reinterpret_cast<const f32x4*>(a.pos + (long)t * D) + cg;
+        f32x4 p[4];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) o[i] = valid ? acc[i] + pr[i] : 0.f;
-    } else {
+        for (int v = 0; v < 4; ++v) p[v] = pr[v * 8];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) o[i] = acc[i];
+        for (int v = 0; v < 4; ++v) o[v * 8] = valid ? acc[v] + p[v] : f32x4{0.f, 0.f, 0.f, 0.f};
+      } else {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) o[v * 8] = acc[v];
+      }
     }
+    if (tin) {                                      // this round's rows of the weight tile: the listed values, 0 elsewhere
+      if (live)
+        for (int j = 0; j < n; ++j) {
+          const int l = ls.l[j];
+          if ((l & 7) == lg && base + j < GU_CAP) wcol[(long)l * T] = Wt[base + j][tt];
+        }
+      const int lend = min(L, l0 + GU_R);
+      for (int l = l0 + lg; l < lend; l += 8)
+        if (!(live && ls.in[l - l0])) wcol[(long)l * T] = 0.f;
+    }
+    if (live) base += n;
+    __syncthreads();
   }
 }
 
 // ---------------------------------------------------------------- backward, phase 1: dw[l,t] = g[t,:] . x'[l,:], Dsum[t] = sum_l w dw
 struct UpBwd1Args {
   const float* g;        // (B, T, D) grad wrt the kernel output (already zero where masked)
-  const float* xp; const float* weights; const int64_t* in_len; const int64_t* out_len;
-  float* dw;             // (B, L, T)
+  const float* xp; const float* weights; const float* means; const float* ranges; const int64_t* in_len; const int64_t* out_len;
+  float* dw;             // (B, L, T), written for the phonemes that reach the tile (dw is only ever used multiplied by w, see bwd2)
   float* dsum;           // (B, T)
   int L, T;
 };
 __global__ __launch_bounds__(256) void gu_upsample_bwd1_kernel(UpBwd1Args a) {
+  __shared__ GuList ls;
   __shared__ float G[TT][D + 1];
   __shared__ float part[8][TT];
-  __shared__ int lrange[2];
   const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * TT;
-  const int L = a.L, T = a.T, len = (int)a.in_len[b];
-  const int tvalid = a.out_len ? (int)a.out_len[b] : T;
-  if (tid == 0) { lrange[0] = 1 << 30; lrange[1] = -1; }
-  __syncthreads();
-  {   // phonemes with a non-zero weight on this tile (dw is only ever used multiplied by w, see bwd2)
-    const int tt = tid & 31, lg = tid >> 5;
-    int lo = 1 << 30, hi = -1;
-    if (t0 + tt < T)
-      for (int l = lg; l < len; l += 8)
-        if (a.weights[((long)b * L + l) * T + t0 + tt] != 0.f) { lo = min(lo, l); hi = max(hi, l); }
-    if (hi >= 0) { atomicMin(&lrange[0], lo); atomicMax(&lrange[1], hi); }
+  const int L = a.L, T = a.T, len = (int)dx_clamp_len(a.in_len, b, L);
+  const int tvalid = a.out_len ? (int)dx_clamp_len(a.out_len, b, T) : T;
+  if (t0 >= tvalid) {   // bwd2 stops at tvalid: nothing of this tile is read but, for tidiness, Dsum
+    if (tid < TT && t0 + tid < T) a.dsum[(long)b * T + t0 + tid] = 0.f;
+    return;
   }
   for (int i = tid; i < TT * D; i += 256) {
     const int r = i / D, c = i - r * D, t = t0 + r;
-    G[r][c] = (t < T && t < tvalid) ? a.g[((long)b * T + t) * D + c] : 0.f;
+    G[r][c] = t < tvalid ? a.g[((long)b * T + t) * D + c] : 0.f;
   }
-  __syncthreads();
   const int tt = tid & 31, lg = tid >> 5;
+  // the list does not depend on out_len (t1 is the tile's end, not tvalid), so the order of the sums below does not either
+  const int t1 = min(t0 + TT, T) - 1;
   float dacc = 0.f;
-  const int lfirst = lrange[0], llast = min(lrange[1], len - 1);
-  for (int l = lfirst + lg; l <= llast; l += 8) {
-    float dot = 0.f;
-    {
-      const float* xr = a.xp + ((long)b * L + l) * D;
-      for (int c = 0; c < D; ++c) dot = fmaf(G[tt][c], xr[c], dot);
+  for (int l0 = 0; l0 < len; l0 += GU_R) {
+    const int n = gu_compact(ls, a.means + (long)b * L, a.ranges + (long)b * L, l0, len, t0, t1);   // its barriers also cover G
+    for (int j = lg; j < n; j += 8) {
+      const int l = ls.l[j];
+      const f32x4* xr = reinterpret_cast<const f32x4*>(a.xp + ((long)b * L + l) * D);
+      float dot = 0.f;
+      for (int c4 = 0; c4 < D / 4; ++c4) {
+        const f32x4 x = xr[c4];
+        dot = fmaf(G[tt][c4 * 4 + 0], x[0], dot); dot = fmaf(G[tt][c4 * 4 + 1], x[1], dot);
+        dot = fmaf(G[tt][c4 * 4 + 2], x[2], dot); dot = fmaf(G[tt][c4 * 4 + 3], x[3], dot);
+      }
+      if (t0 + tt < T) {
+        const long idx = ((long)b * L + l) * T + t0 + tt;
+        a.dw[idx] = dot;
+        dacc += a.weights[idx] * dot;
+      }
     }
-    if (t0 + tt < T) {
-      const long idx = ((long)b * L + l) * T + t0 + tt;
-      a.dw[idx] = dot;
-      dacc += a.weights[idx] * dot;
-    }
+    __syncthreads();
   }
   part[lg][tt] = dacc;
   __syncthreads();
@@ -225,6 +322,8 @@ __global__ __launch_bounds__(256) void gu_upsample_bwd1_kernel(UpBwd1Args a) {
 // ---------------------------------------------------------------- backward, phase 2 (one workgroup per (b,l)):
 //   dxp[l,:] = sum_t w[l,t] g[t,:];   dsigma[l] = sum_t w[l,t] (dw[l,t] - Dsum[t]) ((t+.5-mu)^2/s^3 - 1/s)
 //   dr = dsigma * sigmoid(r_pre);  dxp += dr * w_r;  d(range weight) and d(duration projection) handled by the caller
+// t runs over the phoneme's reach clipped to the valid frames.  Eight groups of 32 threads (four channels each) take every eighth
+// frame of it, so eight rows of g are in flight at once; the eight partial rows are then added in the fixed order k = 0..7.
 struct UpBwd2Args {
   const float* g; const float* weights; const float* dw; const float* dsum; const float* means; const float* ranges;
   const float* r_pre; const float* w_r; const int64_t* in_len; const int64_t* out_len;
@@ -233,52 +332,59 @@ struct UpBwd2Args {
   float* dr;         // (B, L)
   int L, T;
 };
-__global__ __launch_bounds__(128) void gu_upsample_bwd2_kernel(UpBwd2Args a) {
-  __shared__ float red[2];
-  const int c = threadIdx.x, l = blockIdx.x, b = blockIdx.y;
-  const int L = a.L, T = a.T, len = (int)a.in_len[b];
+__global__ __launch_bounds__(256) void gu_upsample_bwd2_kernel(UpBwd2Args a) {
+  __shared__ float racc[8][D];
+  __shared__ float red[4];
+  const int tid = threadIdx.x, l = blockIdx.x, b = blockIdx.y;
+  const int L = a.L, T = a.T, len = (int)dx_clamp_len(a.in_len, b, L);
   const long row = (long)b * L + l;
   float* dxp = a.dxp + row * D;
   float* drin = a.drin + row * D;
+  const int tvalid = a.out_len ? (int)dx_clamp_len(a.out_len, b, T) : T;
+  // row < B * L whatever len is: these come back in one round trip with the lengths
+  const float mu = a.means[row], sd = a.ranges[row], rp = a.r_pre[row], wr = a.w_r[tid & (D - 1)];
   if (l >= len) {
-    dxp[c] = 0.f; drin[c] = 0.f;
-    if (c == 0) a.dr[row] = 0.f;
+    if (tid < D) { dxp[tid] = 0.f; drin[tid] = 0.f; }
+    if (tid == 0) a.dr[row] = 0.f;
     return;
   }
-  const int tvalid = min(T, a.out_len ? (int)a.out_len[b] : T);
   const float* w = a.weights + row * T;
   const float* dwr = a.dw + row * T;
   const float* ds = a.dsum + (long)b * T;
-  const float mu = a.means[row], sd = a.ranges[row];
-  // frames on which this phoneme's weight is not exactly zero (a band around its Gaussian mean)
-  __shared__ int trange[2];
-  if (c == 0) { trange[0] = 1 << 30; trange[1] = -1; }
-  __syncthreads();
-  {
-    int lo = 1 << 30, hi = -1;
-    for (int t = c; t < tvalid; t += 128) if (w[t] != 0.f) { lo = min(lo, t); hi = max(hi, t); }
-    if (hi >= 0) { atomicMin(&trange[0], lo); atomicMax(&trange[1], hi); }
+  int lo, hi;
+  gu_reach(mu, sd, logf(sd), lo, hi);
+  const int tfirst = max(lo, 0), tlast = min(hi, tvalid - 1);   // 0 <= t < tvalid <= T inside both loops
+  const int fg = tid >> 5, cq = tid & 31;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  const float* gb = a.g + (long)b * T * D + cq * 4;
+#pragma unroll 2
+  for (int t = tfirst + fg; t <= tlast; t += 8) {
+    const float wt = w[t];
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(gb + (long)t * D);
+    acc[0] = fmaf(wt, gv[0], acc[0]); acc[1] = fmaf(wt, gv[1], acc[1]);
+    acc[2] = fmaf(wt, gv[2], acc[2]); acc[3] = fmaf(wt, gv[3], acc[3]);
   }
-  __syncthreads();
-  const int tfirst = trange[0], tlast = trange[1];
-  float acc = 0.f, dsig = 0.f;
-  for (int t = tfirst; t <= tlast; ++t) acc = fmaf(w[t], a.g[((long)b * T + t) * D + c], acc);
-  for (int t = tfirst + c; t <= tlast; t += 128) {
+  float dsig = 0.f;
+  for (int t = tfirst + tid; t <= tlast; t += 256) {
     const float wt = w[t];
     if (wt != 0.f) {
       const float dlt = (float)t + 0.5f - mu;
       dsig += wt * (dwr[t] - ds[t]) * (dlt * dlt / (sd * sd * sd) - 1.f / sd);
     }
   }
-  dsig = dx_wave_sum(dsig);
-  if ((c & 63) == 0) red[c >> 6] = dsig;
-  __syncthreads();
-  const float rp = a.r_pre[row];
-  const float dr = (red[0] + red[1]) * (rp > 20.f ? 1.f : 1.f / (1.f + expf(-rp)));
-  const float dri = dr * a.w_r[c];
-  dxp[c] = acc + dri;
-  drin[c] = dri;
-  if (c == 0) a.dr[row] = dr;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) racc[fg][cq * 4 + i] = acc[i];
+  dsig = dx_block_sum<4, false>(dsig, red);   // its barrier also publishes racc
+  if (tid < D) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += racc[k][tid];
+    const float dr = dsig * (rp > 20.f ? 1.f : 1.f / (1.f + expf(-rp)));
+    const float dri = dr * wr;
+    dxp[tid] = s + dri;
+    drin[tid] = dri;
+    if (tid == 0) a.dr[row] = dr;
+  }
 }
 
 }  // namespace
@@ -325,10 +431,10 @@ extern "C" int dx_gu_upsample_bwd(const float* g, const float* xp, const float* 
              DX_ERR_ARG, "dx_gu_upsample_bwd: null pointer");
   DX_REQUIRE(C == D, DX_ERR_UNSUPPORTED, "dx_gu_upsample_bwd: C=%d (only 128)", C);
   hipStream_t s = (hipStream_t)stream;
-  UpBwd1Args a1{g, xp, weights, in_lengths, out_lengths, dw_ws, dsum_ws, L, T};
+  UpBwd1Args a1{g, xp, weights, means, ranges, in_lengths, out_lengths, dw_ws, dsum_ws, L, T};
   hipLaunchKernelGGL(gu_upsample_bwd1_kernel, dim3(dx_cdiv(T, TT), B), dim3(256), 0, s, a1);
   UpBwd2Args a2{g, weights, dw_ws, dsum_ws, means, ranges, r_pre, w_range, in_lengths, out_lengths, dxp, drin, dr, L, T};
-  hipLaunchKernelGGL(gu_upsample_bwd2_kernel, dim3(L, B), dim3(128), 0, s, a2);
+  hipLaunchKernelGGL(gu_upsample_bwd2_kernel, dim3(L, B), dim3(256), 0, s, a2);
   DX_LAUNCH_CHECK();
   return DX_OK;
 }
