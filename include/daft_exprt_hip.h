@@ -446,7 +446,8 @@ int dx_gu_upsample_bwd(const float* g, const float* xp, const float* weights, co
  * d_post_mult is ACCUMULATED.  w_spk is the ramped adversarial weight (loss.py:22-28).
  * ws: NULL, or dx_loss_ws_floats(B, T) floats of scratch (no initialisation): with it (and the transposed mel gradient) the
  * per-workgroup terms are added in a fixed order by the last of THREE launches -- run-to-run identical loss terms, no same-address
- * atomics; without it four launches and fp32 atomics on terms[2..6]. */
+ * atomics; without it four launches and fp32 atomics on terms[2..6].  With n_mel > 128 (the transposed-tile kernel's limit) ws is
+ * ignored.  B, L, T, n_mel and n_spk_classes must be positive and n_post >= 0 (DX_ERR_SHAPE); every length >= 1. */
 long dx_loss_ws_floats(int B, int T);
 int dx_loss_fwd_bwd(const float* dur, const float* energy, const float* pitch, const float* dur_t,
                     const float* energy_t, const float* pitch_t, const int64_t* in_lengths, const float* mel,

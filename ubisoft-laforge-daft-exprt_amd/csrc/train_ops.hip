@@ -362,7 +362,7 @@ extern "C" int dx_loss_fwd_bwd(const float* dur, const float* energy, const floa
                                int d_mel_transposed, const DxStepScalars* step, void* stream) {
   DX_REQUIRE(dur && energy && pitch && dur_t && energy_t && pitch_t && in_lengths && mel && mel_t && out_lengths && spk_logits &&
              spk_ids && terms, DX_ERR_ARG, "dx_loss_fwd_bwd: null pointer");
-  DX_REQUIRE(B > 0 && L > 0 && T > 0, DX_ERR_SHAPE, "dx_loss_fwd_bwd: empty shape");
+  DX_REQUIRE(B > 0 && L > 0 && T > 0 && n_mel > 0 && n_spk_classes > 0 && n_post >= 0, DX_ERR_SHAPE, "dx_loss_fwd_bwd: empty shape");
   hipStream_t s = (hipStream_t)stream;
   // ws (dx_loss_ws_floats(B, T) floats, no initialisation): per-workgroup terms added in a fixed order by the last launch (3 launches, no
   // atomics, 4x the workgroups on the mel term); only with the transposed mel gradient (the training step's form).  NULL: atomics, 4 launches.
