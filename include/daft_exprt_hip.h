@@ -1189,6 +1189,44 @@ int dx_vocoder_snake_bwd(const float* x, long ldx, const float* dy, long lddy, c
                          const float* filters, float* dx, long lddx, float* dalpha, float* dinv_beta, void* ws, const int64_t* n_rows,
                          int B, int N, int C, int tile_rows, void* stream);
 
+/* ---- K36: the magnitude spectrogram of a waveform and its gradient back to the waveform -- the one operation BigVGAN's
+ * multi-resolution discriminator (Lee et al. 2023, section 3) adds to fine-tuning (csrc/spectrogram.hip).  Additive entry points (the ABI
+ * version stays).  wav (B, S) fp32, rows ldw floats apart; n_samples (B) int64 on the device; window (n_fft) fp32 on the device, ANY
+ * table (ones on [l, l + win), l = (n_fft - win) div 2, zeros elsewhere is torch.stft's window=None; a Hann table gives a Hann
+ * spectrogram); twiddle (2 n_fft) fp32 from dx_spectrogram_tables (exp(-2 pi i t / n_fft) computed in double).
+ *
+ * dx_spectrogram: per utterance b with n = n_samples[b] and the resolution (n_fft, hop):
+ *     p          = (n_fft - hop) div 2
+ *     x~[s]      = x[r(s - p)],  s in [0, n + 2 p),   r(i) = -i (i < 0), 2 (n - 1) - i (i >= n), i otherwise        (torch's 'reflect')
+ *     F_b        = 1 + (n + 2 p - n_fft) div hop
+ *     X[f, k]    = sum_j window[j] * x~[f hop + j] * exp(-2 pi i j k / n_fft),   k in [0, n_fft / 2]
+ *     mag[b,k,f] = sqrt(re^2 + im^2)                                (no epsilon: torch.norm of torch.stft(center=False))
+ *   mag (B, n_fft / 2 + 1, T) fp32, contiguous; frames F_b .. T are written as zeros; wav samples at or past n_samples[b] are NEVER READ.
+ * dx_spectrogram_bwd: nothing is saved by the forward, X is recomputed.  dmag (B, n_fft / 2 + 1, T) fp32, contiguous:
+ *     G[f, k]    = dmag[b,k,f] * X[f, k] / |X[f, k]|,   0 where |X| = 0                  (torch's norm backward: never NaN)
+ *     dy_f[j]    = window[j] * Re sum_{k = 0}^{n_fft / 2} G[f, k] * exp(+2 pi i j k / n_fft)    (the one-sided sum: bins are not doubled)
+ *     dx~[s]     = sum_{f in [0, F_b) : 0 <= s - f hop < n_fft} dy_f[s - f hop]
+ *     dx[i]      = dx~[i + p]  +  (1 <= i <= p ? dx~[p - i] : 0)  +  (n - 1 - p <= i <= n - 2 ? dx~[p + 2 (n - 1) - i] : 0)
+ *   dwav (B, S) fp32, rows lddw floats apart; samples n_samples[b] .. S are written as zeros; dmag frames at or past F_b and wav samples at
+ *   or past n_samples[b] are NEVER READ.  No atomics: one launch writes every live frame's dy_f to ws, a second gathers each sample's at
+ *   most ceil(n_fft / hop) frames in ascending frame order and then the two folds in the order written above -- two calls give the same
+ *   bits, and an utterance gets the same bits alone, in any batch and at any T.
+ *   ws         dx_spectrogram_bwd_workspace(B, T, n_fft) bytes (0 for a non-positive argument), 4-byte aligned; nothing in it has to be
+ *              initialised.
+ * n_samples_host: a HOST array of the same B values as n_samples, which the launcher checks before any launch: n <= p or n + 2 p < n_fft
+ * (torch refuses the same padding) returns DX_ERR_UNSUPPORTED naming the utterance, as do an n_fft outside {256, 512, 1024, 2048, 4096} and
+ * a hop outside [1, n_fft]; n > S, F_b > T, ldw or lddw < S, B > 65535 or a non-positive B, S, T return DX_ERR_SHAPE; a NULL pointer
+ * DX_ERR_ARG.  The kernels read the device copy and give an utterance that fails these conditions there no frame (mag and dwav zeros), so
+ * no index leaves a buffer whatever n_samples holds.  fp32 throughout; one workgroup of n_fft / 4 threads and 16 n_fft bytes of LDS per
+ * frame (the radix-4 Stockham loop of the audio kernels closed by one radix-2 stage for 512 and 2048). */
+int dx_spectrogram_tables(float* twiddle, int n_fft, void* stream);
+int dx_spectrogram(const float* wav, long ldw, const int64_t* n_samples, const int64_t* n_samples_host, const float* twiddle,
+                   const float* window, float* mag, int B, int S, int T, int n_fft, int hop, void* stream);
+long dx_spectrogram_bwd_workspace(int B, int T, int n_fft);
+int dx_spectrogram_bwd(const float* wav, long ldw, const int64_t* n_samples, const int64_t* n_samples_host, const float* twiddle,
+                       const float* window, const float* dmag, float* dwav, long lddw, void* ws, int B, int S, int T, int n_fft, int hop,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

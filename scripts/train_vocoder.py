@@ -2,7 +2,7 @@
 """Fine-tune a HiFi-GAN or BigVGAN vocoder on the fine-tuning data set, on the GPU
     python scripts/train_vocoder.py -ft FINE_TUNING_DATASET -cfg CONFIG_JSON -g G_CKPT [-do DO_CKPT] -o OUT_DIR [--steps 1000]
                                     [--batch_size 16] [--segment_size 8192] [--compute_dtype fp32] [--checkpoint_interval 500]
-                                    [--seed 1234]
+                                    [--seed 1234] [--second_discriminator msd]
 
   -ft    the `fine_tuning_dataset` directory `daft_exprt/fine_tune.py` writes: `<speaker>/<file>.npy` (teacher-forced mel) and
          `<speaker>/<file>.wav` (the cropped recording) per utterance
@@ -10,7 +10,12 @@
          an `activation` key, BigVGAN's (the 512-channel base models qualify, the 1536-channel models' 48- / 24-channel tail does not)
   -g     the pretrained generator checkpoint `g_XXXXXXXX`
   -do    the discriminator / optimiser checkpoint `do_XXXXXXXX` of THIS script to continue from; without it the discriminators
-         (multi-period and multi-scale for either family: an upstream BigVGAN `do_` file is not read) start from their initialisation
+         start from their initialisation.  A file written with the other --second_discriminator is refused
+  --second_discriminator  what trains beside the multi-period discriminator, for either generator family: `msd`, HiFi-GAN's multi-scale
+         discriminator and recipe (lr 2e-4), or `mrd`, BigVGAN's multi-resolution discriminator (2-D convs over magnitude spectrograms at
+         the config's `resolutions`, default [[1024, 120, 600], [2048, 240, 1200], [512, 50, 240]]) under BigVGAN's recipe: the config's
+         `learning_rate` (default 1e-4) and `clip_grad_norm` (default 1000).  `do_%08d` then holds `mrd` in place of `msd`; that an
+         upstream BigVGAN `do_` file loads has not been verified
   -o     directory the checkpoints `g_%08d` / `do_%08d`, a copy of `config.json` and `vocoder_report.json` are written to;
          `scripts/synthesize.py -voc OUT_DIR/g_%08d` reads the result
 
@@ -44,6 +49,8 @@ def parse_args(argv=None):
     parser.add_argument('--compute_dtype', default='fp32', choices=['fp32', 'bf16'], help="the generator's MFMA operand type")
     parser.add_argument('--checkpoint_interval', type=int, default=500, help='steps between checkpoints / validations')
     parser.add_argument('--seed', type=int, default=1234, help='seed of the segments and the discriminators')
+    parser.add_argument('--second_discriminator', default='msd', choices=['msd', 'mrd'],
+                        help="beside the MPD: HiFi-GAN's multi-scale (msd) or BigVGAN's multi-resolution (mrd) discriminator")
     return parser.parse_args(argv)
 
 
@@ -82,7 +89,8 @@ def main(argv=None):
     try:
         report = fine_tune_vocoder(config, args.fine_tuning_dataset, args.generator, args.discriminators, out_dir=args.output_dir,
                                    steps=args.steps, batch_size=args.batch_size, segment_size=args.segment_size,
-                                   compute_dtype=args.compute_dtype, checkpoint_interval=args.checkpoint_interval, seed=args.seed)
+                                   compute_dtype=args.compute_dtype, checkpoint_interval=args.checkpoint_interval, seed=args.seed,
+                                   second_discriminator=args.second_discriminator)
     except ValueError as e:                      # a mel of another hop / bin count, a short data set, a foreign checkpoint
         raise SystemExit(f'train_vocoder.py: {e}')
     path = os.path.join(args.output_dir, 'vocoder_report.json')

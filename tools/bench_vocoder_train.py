@@ -14,7 +14,13 @@ weights from a seed) on the same batch and segment: its forward + backward ms in
 forward (`dx_vocoder_snake`) and backward (`dx_vocoder_snake_bwd`, with its reduce launch) alone, 20 launches per timed window -- ms, bytes (forward: x read and y
 written; backward: x and dy read, dx written), TB/s, the rate against a float copy of the same bytes timed in the same run, the
 tile height the backward's launcher chose -- and both launches' share of the generator's forward + backward.
-Run:  python tools/bench_vocoder_train.py [--reps 5] [--batch 16] [--segment 8192] [--bigvgan]
+
+`--mrd` adds, under "mrd", the fp32 step against MPD + BigVGAN's multi-resolution discriminator (`bigvgan_train`, under its recipe's
+gradient clipping) beside the step against MPD + MSD, and per resolution the spectrogram launches alone (K36: `dx_spectrogram`, and
+`dx_spectrogram_bwd` with its gather launch), 20 calls per timed window, against `torch.stft` + `torch.norm` + autograd on the same
+device and waveforms -- a yardstick that lives here only -- and the share of a step that K36 takes: per resolution four forwards (y and
+y_hat in either half of the step) and one backward.
+Run:  python tools/bench_vocoder_train.py [--reps 5] [--batch 16] [--segment 8192] [--bigvgan] [--mrd]
 """
 import argparse
 import json
@@ -256,12 +262,78 @@ def bigvgan(args, base_cfg, mel, proj, lengths, dev):
     return out
 
 
+def mrd(args, cfg, sd, mel, audio, loss_mel, dev):
+    ''' the "mrd" entry of the result '''
+    from daft_exprt import bigvgan_train as BT
+    from daft_exprt import vocoder_train as VT
+    from daft_exprt.spectrogram import spectrogram
+    out = {}
+    for second in ('msd', 'mrd'):
+        torch.manual_seed(0)
+        generator = VT.TrainableGenerator(cfg, sd, compute_dtype='fp32').to(dev)
+        mpd = VT.MultiPeriodDiscriminator().to(dev)
+        other = (VT.MultiScaleDiscriminator() if second == 'msd' else BT.MultiResolutionDiscriminator(cfg)).to(dev)
+        lr, clip = (VT.LEARNING_RATE, None) if second == 'msd' else (VT.MRD_LEARNING_RATE, VT.MRD_CLIP_GRAD_NORM)
+        optim_g = torch.optim.AdamW(generator.parameters(), lr, betas=VT.ADAM_BETAS)
+        optim_d = torch.optim.AdamW(list(other.parameters()) + list(mpd.parameters()), lr, betas=VT.ADAM_BETAS)
+        step = lambda: VT.train_step(generator, mpd, other, optim_g, optim_d, loss_mel, mel, audio, clip_grad_norm=clip)      # noqa: E731
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        out[f'mpd_{second}_ms_per_step'] = _timed(step, args.reps)
+        del generator, mpd, other, optim_g, optim_d
+        torch.cuda.empty_cache()
+    counts, k36_ms, entries = [args.segment] * args.batch, 0., []
+    for n_fft, hop, win in BT.MRD_RESOLUTIONS:
+        x = audio.clone().requires_grad_(True)
+        mag, frames = spectrogram(x, counts, n_fft, hop, win=win)
+        dmag = torch.randn_like(mag)
+        p = (n_fft - hop) // 2
+
+        def hip_fwd():
+            with torch.no_grad():
+                spectrogram(audio, counts, n_fft, hop, win=win)
+
+        def hip_fwd_bwd():
+            x.grad = None
+            spectrogram(x, counts, n_fft, hop, win=win)[0].backward(dmag)
+
+        def stft_mag(w):
+            spec = torch.stft(F.pad(w[:, None], (p, p), mode='reflect')[:, 0], n_fft, hop_length=hop, win_length=win, window=None,
+                              center=False, return_complex=True)
+            return torch.norm(torch.view_as_real(spec), p=2, dim=-1)
+
+        def torch_fwd():
+            with torch.no_grad():
+                stft_mag(audio)
+
+        def torch_fwd_bwd():
+            x.grad = None
+            stft_mag(x).backward(dmag)
+        assert tuple(stft_mag(audio).shape) == tuple(mag.shape)
+        ms = {}
+        for name, fn in (('k36_forward', hip_fwd), ('k36_forward_backward', hip_fwd_bwd), ('torch_stft_forward', torch_fwd),
+                         ('torch_stft_forward_backward', torch_fwd_bwd)):
+            fn()
+            fn()
+            torch.cuda.synchronize()
+            ms[name + '_ms'] = _timed(lambda fn=fn: [fn() for _ in range(LAUNCHES)], args.reps) / LAUNCHES
+        ms['forward_speedup'] = ms['torch_stft_forward_ms'] / ms['k36_forward_ms']
+        ms['forward_backward_speedup'] = ms['torch_stft_forward_backward_ms'] / ms['k36_forward_backward_ms']
+        k36_ms += 3 * ms['k36_forward_ms'] + ms['k36_forward_backward_ms']
+        entries.append(dict({'n_fft': n_fft, 'hop': hop, 'win': win, 'frames_per_batch': int(frames.sum())}, **ms))
+    out['resolutions'] = entries
+    out['k36_ms_per_step'], out['k36_share_of_step'] = k36_ms, k36_ms / out['mpd_mrd_ms_per_step']
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--segment', type=int, default=8192)
     ap.add_argument('--bigvgan', action='store_true', help='also measure a BigVGAN generator of the base layout (V1 + snakebeta)')
+    ap.add_argument('--mrd', action='store_true', help="also measure the step against BigVGAN's multi-resolution discriminator and K36")
     args = ap.parse_args()
     warnings.simplefilter('ignore')
     from daft_exprt import vocoder_train as VT
@@ -312,10 +384,12 @@ def main():
         torch_fwd_bwd()
     torch.cuda.synchronize()
     out['torch_conv1d_generator_forward_backward_ms'] = _timed(torch_fwd_bwd, args.reps)
+    del tw
+    torch.cuda.empty_cache()
     if args.bigvgan:
-        del tw
-        torch.cuda.empty_cache()
         out['bigvgan'] = bigvgan(args, cfg, mel, proj, lengths, dev)
+    if args.mrd:
+        out['mrd'] = mrd(args, cfg, sd, mel, audio, loss_mel, dev)
     print(json.dumps(out))
 
 

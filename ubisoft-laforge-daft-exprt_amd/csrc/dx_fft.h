@@ -72,3 +72,67 @@ __device__ __forceinline__ int dx_fft_lds(float (*bufr)[NFFT], float (*bufi)[NFF
   }
   return cur;
 }
+
+// ---- every power of two from 256 to 4096 (K36, spectrogram.hip: the multi-resolution discriminator's 512 and 2048) ------------
+// A dispatch of its own: dx_nfft_dispatch / dx_nfft_ok above state what the front end and Griffin-Lim accept, and stay as they are.
+template <typename F>
+static inline bool dx_nfft2_dispatch(int n_fft, F&& f) {
+  switch (n_fft) {
+    case 256: f(std::integral_constant<int, 256>{}); return true;
+    case 512: f(std::integral_constant<int, 512>{}); return true;
+    case 1024: f(std::integral_constant<int, 1024>{}); return true;
+    case 2048: f(std::integral_constant<int, 2048>{}); return true;
+    case 4096: f(std::integral_constant<int, 4096>{}); return true;
+  }
+  return false;
+}
+static inline bool dx_nfft2_ok(int n_fft) { return dx_nfft2_dispatch(n_fft, [](auto) {}); }
+
+// dx_fft_lds for any power of two NFFT >= 4: the radix-4 Stockham stages while 4 Ns <= NFFT -- the same butterfly, so a power of 4
+// gives dx_fft_lds's bits -- closed, where NFFT = 2 * 4^m, by ONE radix-2 stage (Ns = NFFT / 2: butterfly k reads k and k + NFFT / 2,
+// twiddle k, writes k and k + NFFT / 2; two butterflies per thread).  NFFT / 4 threads, one barrier per stage; same buffers and return.
+template <int NFFT>
+__device__ __forceinline__ int dx_fft_lds2(float (*bufr)[NFFT], float (*bufi)[NFFT], int cur, const float* twiddle, int j) {
+  constexpr int NT = NFFT / 4;
+#pragma unroll
+  for (int Ns = 1; Ns * 4 <= NFFT; Ns *= 4) {
+    const int k = j & (Ns - 1);
+    cplx v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = {bufr[cur][j + r * NT], bufi[cur][j + r * NT]};
+    if (Ns > 1) {
+      const int t = k * (NFFT / (4 * Ns));                        // angle = -2 pi k / (4 Ns)
+#pragma unroll
+      for (int r = 1; r < 4; ++r) {
+        const cplx w = {twiddle[2 * (r * t)], twiddle[2 * (r * t) + 1]};
+        v[r] = cmul(v[r], w);
+      }
+    }
+    const cplx s02 = {v[0].re + v[2].re, v[0].im + v[2].im}, d02 = {v[0].re - v[2].re, v[0].im - v[2].im};
+    const cplx s13 = {v[1].re + v[3].re, v[1].im + v[3].im}, d13 = {v[1].re - v[3].re, v[1].im - v[3].im};
+    const cplx y0 = {s02.re + s13.re, s02.im + s13.im}, y2 = {s02.re - s13.re, s02.im - s13.im};
+    const cplx y1 = {d02.re + d13.im, d02.im - d13.re};           // d02 - i d13
+    const cplx y3 = {d02.re - d13.im, d02.im + d13.re};           // d02 + i d13
+    const int o = (j - k) * 4 + k;                                // (j / Ns) * 4 Ns + k
+    bufr[cur ^ 1][o] = y0.re; bufi[cur ^ 1][o] = y0.im;
+    bufr[cur ^ 1][o + Ns] = y1.re; bufi[cur ^ 1][o + Ns] = y1.im;
+    bufr[cur ^ 1][o + 2 * Ns] = y2.re; bufi[cur ^ 1][o + 2 * Ns] = y2.im;
+    bufr[cur ^ 1][o + 3 * Ns] = y3.re; bufi[cur ^ 1][o + 3 * Ns] = y3.im;
+    cur ^= 1;
+    __syncthreads();
+  }
+  if constexpr (__builtin_ctz(NFFT) & 1) {                        // NFFT = 2 * 4^m: Ns = NFFT / 2
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = j + h * NT;
+      const cplx a = {bufr[cur][k], bufi[cur][k]};
+      const cplx w = {twiddle[2 * k], twiddle[2 * k + 1]};        // angle = -2 pi k / NFFT
+      const cplx b = cmul(cplx{bufr[cur][k + NFFT / 2], bufi[cur][k + NFFT / 2]}, w);
+      bufr[cur ^ 1][k] = a.re + b.re; bufi[cur ^ 1][k] = a.im + b.im;
+      bufr[cur ^ 1][k + NFFT / 2] = a.re - b.re; bufi[cur ^ 1][k + NFFT / 2] = a.im - b.im;
+    }
+    cur ^= 1;
+    __syncthreads();
+  }
+  return cur;
+}

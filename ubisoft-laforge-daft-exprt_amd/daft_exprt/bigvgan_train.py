@@ -11,8 +11,13 @@ writer are that module's; this one adds
 
 `TrainableBigVGAN` is `TrainableGenerator` (one construction of the layer parameters) with these in its forward, which follows
 `vocoder.activation_table`.  Every stage must be a multiple of 32 channels, as for HiFi-GAN: the 512-channel base models qualify, the
-1536-channel models' 48- / 24-channel tail is refused (training on zero-padded stages is not built).  The discriminators stay the
-project's MPD / MSD: an upstream BigVGAN `do_` file (MPD and a multi-resolution discriminator) is not read.  No CPU fallback.
+1536-channel models' 48- / 24-channel tail is refused (training on zero-padded stages is not built).  No CPU fallback.
+
+    the discriminator   `MultiResolutionDiscriminator` / `DiscriminatorR`, restated from the paper: 2-D conv stacks (plain torch, as
+                        MPD / MSD) over the magnitude spectrogram at three STFT resolutions, which with its gradient back to the waveform
+                        is K36 (`daft_exprt/spectrogram.py`, csrc/spectrogram.hip).  `fine_tune_vocoder(second_discriminator='mrd')`
+                        trains MPD + MRD under BigVGAN's recipe and files it under `mrd` in the `do_` checkpoint.  No upstream `do_` file
+                        has been loaded: the module and key names follow what `weight_norm` gives modules of upstream's names.
 """
 import ctypes
 
@@ -220,3 +225,82 @@ class TrainableBigVGAN(VT.TrainableGenerator):
 
     def _post(self, x, n):
         return _PostUngated.apply(x, self.conv_post.weight(), self.conv_post.bias, n, self.final_clamp)
+
+
+# ---- the multi-resolution discriminator (Lee et al. 2023, section 3 and appendix; after UnivNet), plain torch over K36 --------------
+
+MRD_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))     # (n_fft, hop, win)
+
+
+def _hip_spectrogram(wav, n_fft, hop, win):
+    ''' the default `spectrogram=` hook: `daft_exprt.spectrogram.spectrogram` (K36) over whole rows -> (B, bins, T) '''
+    from daft_exprt.spectrogram import spectrogram
+    return spectrogram(wav, [wav.shape[1]] * wav.shape[0], n_fft, hop, win=win)[0]
+
+
+class DiscriminatorR(nn.Module):
+    ''' one resolution (n_fft, hop, win): the magnitude spectrogram (B, 1, bins, T) -- reflect padding of (n_fft - hop) div 2, a
+        rectangular window of `win` samples, no centring -- through Conv2d(1, 32 c, (3, 9)), three Conv2d(32 c, 32 c, (3, 9)) of stride
+        (1, 2), Conv2d(32 c, 32 c, (3, 3)) and conv_post = Conv2d(32 c, 1, (3, 3)); leaky-ReLU 0.1 after each but the last.
+        `spectrogram(wav (B, S), n_fft, hop, win) -> (B, bins, T)` replaces the HIP op (the host tests pass the CPU oracle). '''
+    def __init__(self, resolution, channel_mult=1, use_spectral_norm=False, spectrogram=None):
+        super().__init__()
+        if len(resolution) != 3:
+            raise ValueError(f'DiscriminatorR: a resolution is (n_fft, hop, win), got {resolution!r}')
+        self.resolution = tuple(int(v) for v in resolution)
+        self._spectrogram = _hip_spectrogram if spectrogram is None else spectrogram
+        c = int(32 * channel_mult)
+        convs = [nn.Conv2d(1, c, (3, 9), padding=(1, 4))]
+        convs += [nn.Conv2d(c, c, (3, 9), stride=(1, 2), padding=(1, 4)) for _ in range(3)]
+        convs.append(nn.Conv2d(c, c, (3, 3), padding=(1, 1)))
+        self.convs = nn.ModuleList(VT._normed(conv, use_spectral_norm) for conv in convs)
+        self.conv_post = VT._normed(nn.Conv2d(c, 1, (3, 3), padding=(1, 1)), use_spectral_norm)
+
+    def check_segment(self, S):
+        ''' raises ValueError naming the resolution where a segment of S samples is too short for it '''
+        n_fft, hop, win = self.resolution
+        p = (n_fft - hop) // 2
+        if S <= p or S + 2 * p < n_fft:
+            raise ValueError(f'DiscriminatorR: a segment of {S} samples is too short for the resolution (n_fft {n_fft}, hop {hop}, '
+                             f'win {win}): reflect padding of {p} per side needs more than {p} samples')
+
+    def forward(self, x):
+        ''' x (B, 1, S) -> (scores (B, -1), feature maps) '''
+        n_fft, hop, win = self.resolution
+        self.check_segment(x.shape[2])
+        x = self._spectrogram(x[:, 0], n_fft, hop, win)[:, None]
+        fmap = []
+        for conv in self.convs:
+            x = F.leaky_relu(conv(x), VT.D_SLOPE)
+            fmap.append(x)
+        x = self.conv_post(x)
+        fmap.append(x)
+        return x.flatten(1), fmap
+
+
+class MultiResolutionDiscriminator(nn.Module):
+    ''' one `DiscriminatorR` per entry of the config's `resolutions` (default: the paper's three); `discriminator_channel_mult` and
+        `use_spectral_norm` as upstream's config names them.  Returns what MPD / MSD return, so `train_step` takes it in their place. '''
+    def __init__(self, config=None, spectrogram=None):
+        super().__init__()
+        config = config or {}
+        resolutions = config.get('resolutions', MRD_RESOLUTIONS)
+        if not resolutions:
+            raise ValueError('MultiResolutionDiscriminator: the config\'s "resolutions" is empty')
+        self.discriminators = nn.ModuleList(
+            DiscriminatorR(r, config.get('discriminator_channel_mult', 1), bool(config.get('use_spectral_norm', False)), spectrogram)
+            for r in resolutions)
+
+    def check_segment(self, S):
+        for d in self.discriminators:
+            d.check_segment(S)
+
+    def forward(self, y, y_hat):
+        ''' y, y_hat (B, 1, S) -> (scores of y, scores of y_hat, feature maps of y, feature maps of y_hat), one entry per resolution '''
+        out = [[], [], [], []]
+        for d in self.discriminators:
+            for k, x in enumerate((y, y_hat)):
+                score, fmap = d(x)
+                out[k].append(score)
+                out[2 + k].append(fmap)
+        return tuple(out)

@@ -629,26 +629,44 @@ class SegmentSampler:
 
 # ---- checkpoints ----------------------------------------------------------------------------------------------------------------
 
-def save_checkpoints(out_dir, config, generator, mpd, msd, optim_g, optim_d, steps, epoch):
-    ''' HiFi-GAN's layout: g_%08d = {'generator'}, do_%08d = {'mpd', 'msd', 'optim_g', 'optim_d', 'steps', 'epoch'}, config.json '''
+SECOND_DISCRIMINATORS = ('msd', 'mrd')      # what trains beside the MPD: HiFi-GAN's multi-scale or BigVGAN's multi-resolution one
+
+
+def _second_key(second):
+    if second not in SECOND_DISCRIMINATORS:
+        raise ValueError(f'second_discriminator is {second!r}, expected "msd" or "mrd"')
+    return second
+
+
+def save_checkpoints(out_dir, config, generator, mpd, msd, optim_g, optim_d, steps, epoch, second='msd'):
+    ''' HiFi-GAN's layout: g_%08d = {'generator'}, do_%08d = {'mpd', 'msd', 'optim_g', 'optim_d', 'steps', 'epoch'}, config.json;
+        `second` = 'mrd' files the module in the `msd` position under BigVGAN's key 'mrd' '''
+    _second_key(second)
     os.makedirs(out_dir, exist_ok=True)
     g_path, do_path = os.path.join(out_dir, f'g_{steps:08d}'), os.path.join(out_dir, f'do_{steps:08d}')
     torch.save({'generator': {k: v.detach().cpu() for k, v in generator.state_dict().items()}}, g_path)
-    torch.save({'mpd': mpd.state_dict(), 'msd': msd.state_dict(), 'optim_g': optim_g.state_dict(), 'optim_d': optim_d.state_dict(),
+    torch.save({'mpd': mpd.state_dict(), second: msd.state_dict(), 'optim_g': optim_g.state_dict(), 'optim_d': optim_d.state_dict(),
                 'steps': steps, 'epoch': epoch}, do_path)
     with open(os.path.join(out_dir, 'config.json'), 'w', encoding='utf-8') as f:
         json.dump(config, f, indent=1)
     return g_path, do_path
 
 
-def load_discriminator_state(do_checkpoint, mpd, msd, optim_g=None, optim_d=None):
+def load_discriminator_state(do_checkpoint, mpd, msd, optim_g=None, optim_d=None, second='msd'):
     ''' (steps, epoch) of a `do_` file loaded into the modules; a key the modules expect and the file lacks raises ValueError
-        naming the first one '''
+        naming the first one.  `second`: the entry the module in the `msd` position is filed under, 'msd' or 'mrd'; a file that holds
+        the other kind raises ValueError naming the entry found and the flag to pass '''
+    _second_key(second)
     state = torch.load(do_checkpoint, map_location='cpu', weights_only=False)
-    for key in ('mpd', 'msd', 'optim_g', 'optim_d', 'steps', 'epoch'):
+    for key in ('mpd', second, 'optim_g', 'optim_d', 'steps', 'epoch'):
+        other = 'mrd' if second == 'msd' else 'msd'
+        if key == second and isinstance(state, dict) and key not in state and other in state:
+            raise ValueError(f'{do_checkpoint}: holds an "{other}" entry and no "{second}": it was trained against the '
+                             f'{"multi-resolution" if other == "mrd" else "multi-scale"} discriminator; pass '
+                             f'second_discriminator="{other}" (scripts/train_vocoder.py --second_discriminator {other})')
         if not isinstance(state, dict) or key not in state:
             raise ValueError(f'{do_checkpoint}: no "{key}" entry (expected a HiFi-GAN discriminator / optimiser checkpoint)')
-    for key, module in (('mpd', mpd), ('msd', msd)):
+    for key, module in (('mpd', mpd), (second, msd)):
         missing = [k for k in module.state_dict() if k not in state[key]]
         if missing:
             raise ValueError(f'{do_checkpoint}: "{key}" has no "{missing[0]}" ({len(missing)} keys missing)')
@@ -663,11 +681,18 @@ def load_discriminator_state(do_checkpoint, mpd, msd, optim_g=None, optim_d=None
 # ---- training -------------------------------------------------------------------------------------------------------------------
 
 LEARNING_RATE, ADAM_BETAS, LR_DECAY = 2e-4, (0.8, 0.99), 0.999
+MRD_LEARNING_RATE, MRD_CLIP_GRAD_NORM = 1e-4, 1000.      # BigVGAN's recipe (Lee et al. 2023, appendix), where the config gives none
 
 
-def train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio):
-    ''' one step of HiFi-GAN's training: the discriminators on the detached synthesis, then the generator.
-        Returns {'disc', 'adv', 'fm', 'mel'} as device scalars (mel = the unweighted L1 of the log-mels) '''
+def _clip(optimizer, max_norm):
+    if max_norm is not None:
+        torch.nn.utils.clip_grad_norm_([p for group in optimizer.param_groups for p in group['params']], max_norm)
+
+
+def train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio, clip_grad_norm=None):
+    ''' one step of HiFi-GAN's training: the discriminators on the detached synthesis, then the generator.  `msd` is the second
+        discriminator, multi-scale or multi-resolution; `clip_grad_norm` (BigVGAN's recipe) clips the gradient norm of each optimiser's
+        parameters before its step.  Returns {'disc', 'adv', 'fm', 'mel'} as device scalars (mel = the unweighted L1 of the log-mels) '''
     B, _, frames = mel.shape
     lengths = torch.full((B,), frames, dtype=torch.int64, device=mel.device)
     y = audio[:, None]
@@ -678,6 +703,7 @@ def train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio):
         real, fake, _, _ = disc(y, y_hat.detach())
         loss_d = loss_d + discriminator_loss(real, fake)
     loss_d.backward()
+    _clip(optim_d, clip_grad_norm)
     optim_d.step()
     optim_g.zero_grad(set_to_none=True)
     l_mel = mel_l1(loss_mel(audio), loss_mel(y_hat[:, 0]))
@@ -687,6 +713,7 @@ def train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio):
         l_adv = l_adv + generator_adversarial_loss(fake)
         l_fm = l_fm + feature_matching_loss(fmap_r, fmap_g)
     (l_adv + l_fm + MEL_LOSS_WEIGHT * l_mel).backward()
+    _clip(optim_g, clip_grad_norm)
     optim_g.step()
     return {'disc': loss_d.detach(), 'adv': l_adv.detach(), 'fm': l_fm.detach(), 'mel': l_mel.detach()}
 
@@ -717,13 +744,17 @@ def held_out_mel_l1(config, state_dict, held_out, compute_dtype, device, centere
 
 def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, out_dir=None, steps=1000, batch_size=16,
                       segment_size=8192, compute_dtype='fp32', checkpoint_interval=500, log_interval=50, validation_fraction=10,
-                      seed=1234, device=None, centered=True):
+                      seed=1234, device=None, centered=True, second_discriminator='msd'):
     ''' fine-tunes the generator of `g_checkpoint` on a `fine_tuning_dataset` (single GPU) and writes `g_%08d` / `do_%08d` /
         `config.json` to `out_dir` at every checkpoint interval and at the end.  AdamW, lr 2e-4, betas (0.8, 0.99), decayed by 0.999
         per epoch; the discriminator step before the generator step.  Without `do_checkpoint` the discriminators start from their
-        initialisation (a warning).  Returns the report `scripts/train_vocoder.py` writes. '''
+        initialisation (a warning).  `second_discriminator`: 'msd', HiFi-GAN's recipe as above for either generator family, or 'mrd',
+        BigVGAN's: MPD + the multi-resolution discriminator (`bigvgan_train.MultiResolutionDiscriminator`, over K36), the config's
+        `learning_rate` (default 1e-4) and `clip_grad_norm` (default 1000, on both optimisers' parameters before their step), the same
+        betas and decay; `do_%08d` then holds 'mrd' in place of 'msd'.  Returns the report `scripts/train_vocoder.py` writes. '''
     config = V.load_config(config)
     V.validate_config(config)
+    _second_key(second_discriminator)
     device = H.device(device)
     hop = int(config['hop_size'])
     if segment_size < hop or segment_size % hop:
@@ -737,12 +768,19 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
     torch.manual_seed(seed)
     loss_mel = LossMel(config).to(device)
     generator = trainable_generator(config, ckpt['generator'], compute_dtype=compute_dtype).to(device)
-    mpd, msd = MultiPeriodDiscriminator().to(device), MultiScaleDiscriminator().to(device)
-    optim_g = torch.optim.AdamW(generator.parameters(), LEARNING_RATE, betas=ADAM_BETAS)
-    optim_d = torch.optim.AdamW(list(msd.parameters()) + list(mpd.parameters()), LEARNING_RATE, betas=ADAM_BETAS)
+    lr, clip = LEARNING_RATE, None
+    if second_discriminator == 'mrd':
+        from daft_exprt.bigvgan_train import MultiResolutionDiscriminator
+        mpd, msd = MultiPeriodDiscriminator().to(device), MultiResolutionDiscriminator(config).to(device)
+        msd.check_segment(segment_size)
+        lr, clip = float(config.get('learning_rate', MRD_LEARNING_RATE)), float(config.get('clip_grad_norm', MRD_CLIP_GRAD_NORM))
+    else:
+        mpd, msd = MultiPeriodDiscriminator().to(device), MultiScaleDiscriminator().to(device)
+    optim_g = torch.optim.AdamW(generator.parameters(), lr, betas=ADAM_BETAS)
+    optim_d = torch.optim.AdamW(list(msd.parameters()) + list(mpd.parameters()), lr, betas=ADAM_BETAS)
     first_step, first_epoch = 0, 0
     if do_checkpoint is not None:
-        first_step, first_epoch = load_discriminator_state(do_checkpoint, mpd, msd, optim_g, optim_d)
+        first_step, first_epoch = load_discriminator_state(do_checkpoint, mpd, msd, optim_g, optim_d, second=second_discriminator)
     else:
         warnings.warn('fine_tune_vocoder: no do_ checkpoint, the discriminators start from their initialisation')
     sampler = SegmentSampler(train, hop, segment_size, device, seed)
@@ -751,7 +789,8 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
     sched_d = torch.optim.lr_scheduler.ExponentialLR(optim_d, gamma=LR_DECAY)
     report = {'utterances_used': len(train), 'utterances_skipped': skipped, 'utterances_held_out': len(held_out),
               'generator_family': 'bigvgan' if V.is_bigvgan(config) else 'hifi-gan', 'compute_dtype': compute_dtype,
-              'batch_size': batch_size, 'segment_size': segment_size, 'first_step': first_step, 'log': []}
+              'batch_size': batch_size, 'segment_size': segment_size, 'first_step': first_step,
+              'second_discriminator': second_discriminator, 'log': []}
     validate = lambda: held_out_mel_l1(config, generator.state_dict(), held_out, compute_dtype, device, centered)   # noqa: E731
     report['held_out_mel_l1_start'] = validate()
     step, epoch, last_val = first_step, max(sampler.epoch, 1), report['held_out_mel_l1_start']
@@ -760,7 +799,7 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
     with torch.cuda.device(device):
         while step < first_step + steps:
             mel, audio = sampler.draw(batch_size)
-            losses = train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio)
+            losses = train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio, clip_grad_norm=clip)
             step += 1
             while epoch < sampler.epoch:                              # the decay of an epoch that ended with this batch's draw
                 sched_g.step()
@@ -776,7 +815,7 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
                     train_s += time.time() - t0
                     last_val = validate()
                     if out_dir is not None:
-                        save_checkpoints(out_dir, config, generator, mpd, msd, optim_g, optim_d, step, sampler.epoch)
+                        save_checkpoints(out_dir, config, generator, mpd, msd, optim_g, optim_d, step, sampler.epoch, second=second_discriminator)
                     t0 = time.time()
                 report['log'].append(dict(values, step=step, held_out_mel_l1=last_val if at_ckpt else None))
                 _logger.info(f'step {step}: ' + ', '.join(f'{k} {v:.4f}' for k, v in values.items()) +
