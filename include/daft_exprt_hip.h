@@ -347,7 +347,8 @@ int dx_embed_pos_fwd(const int64_t* ids, const float* table, const float* pos_ta
 int dx_embed_pos_bwd(const int64_t* ids, const float* dout, const int64_t* lengths, float* dtable, int B, int N, int C,
                      void* stream);
 
-/* ---- K9: out[b] = sum_n x[b, n] / lengths[b] (model.py:419) and its backward. */
+/* ---- K9: out[b] = sum_n x[b, n] / lengths[b] (model.py:419) and its backward dx[b, n] = dy[b] / lengths[b] for all N rows.
+ * An utterance of length 0 has mean 0 and gradient 0. */
 int dx_masked_mean_fwd(const float* x, const int64_t* lengths, float* out, int B, int N, int C, void* stream);
 int dx_masked_mean_bwd(const float* dy, const int64_t* lengths, float* dx, int B, int N, int C, void* stream);
 

@@ -177,7 +177,8 @@ __global__ __launch_bounds__(256) void masked_mean_bwd_kernel(const float* __res
   const long row = (long)blockIdx.x * 2 + (threadIdx.x >> 7);
   if (row >= rows) return;
   const int b = (int)(row / N);
-  dx[row * C128 + c] = dy[b * C128 + c] / (float)lengths[b];
+  const int len = (int)lengths[b];                               // a zero-length utterance has mean 0 (forward), so gradient 0
+  dx[row * C128 + c] = len > 0 ? dy[b * C128 + c] / (float)len : 0.f;
 }
 
 // ------------------------------------------------------------------ FiLM assembly
@@ -439,7 +440,8 @@ __global__ __launch_bounds__(256) void stack_kernel(float* __restrict__ y, Plane
 extern "C" int dx_scalar_embed_fwd(const float* base, const float* const* feats, const float* const* ws,
                                    const float* const* biases, int nfeat, const float* pos_table,
                                    const int64_t* lengths, float* out, int B, int N, int C, int taps, void* stream) {
-  DX_REQUIRE(out && nfeat >= 0 && nfeat <= 3, DX_ERR_ARG, "dx_scalar_embed_fwd: bad arguments");
+  DX_REQUIRE(out && nfeat >= 0 && nfeat <= 3 && (nfeat == 0 || (feats && ws && biases)), DX_ERR_ARG, "dx_scalar_embed_fwd: bad arguments");
+  for (int f = 0; f < nfeat; ++f) DX_REQUIRE(feats[f] && ws[f] && biases[f], DX_ERR_ARG, "dx_scalar_embed_fwd: null feature %d", f);
   DX_REQUIRE(taps == 1 || taps == 3, DX_ERR_UNSUPPORTED, "dx_scalar_embed_fwd: taps=%d (only 1 and 3)", taps);
   DX_REQUIRE(C == C128, DX_ERR_UNSUPPORTED, "dx_scalar_embed_fwd: C=%d (only 128)", C);
   DX_REQUIRE(B > 0 && N > 0, DX_ERR_SHAPE, "dx_scalar_embed_fwd: empty shape");
@@ -454,9 +456,11 @@ extern "C" int dx_scalar_embed_fwd(const float* base, const float* const* feats,
 extern "C" int dx_scalar_embed_bwd(const float* dout, const float* const* feats, int nfeat, const int64_t* lengths,
                                    float* dbase, float* const* dws, float* const* dbiases, int B, int N, int C, int taps,
                                    void* stream) {
-  DX_REQUIRE(dout && nfeat >= 0 && nfeat <= 3, DX_ERR_ARG, "dx_scalar_embed_bwd: bad arguments");
+  DX_REQUIRE(dout && nfeat >= 0 && nfeat <= 3 && (nfeat == 0 || (feats && dws && dbiases)), DX_ERR_ARG, "dx_scalar_embed_bwd: bad arguments");
+  for (int f = 0; f < nfeat; ++f) DX_REQUIRE(feats[f] && dws[f] && dbiases[f], DX_ERR_ARG, "dx_scalar_embed_bwd: null feature %d", f);
   DX_REQUIRE(taps == 1 || taps == 3, DX_ERR_UNSUPPORTED, "dx_scalar_embed_bwd: taps=%d (only 1 and 3)", taps);
   DX_REQUIRE(C == C128, DX_ERR_UNSUPPORTED, "dx_scalar_embed_bwd: C=%d (only 128)", C);
+  DX_REQUIRE(B > 0 && N > 0, DX_ERR_SHAPE, "dx_scalar_embed_bwd: empty shape");
   ScalarEmbedBwdArgs a{};
   a.dout = dout; a.nfeat = nfeat; a.lengths = lengths; a.dbase = dbase; a.N = N; a.taps = taps;
   // every workgroup ends with 512-1024 atomics on the same few addresses: few, fat workgroups
@@ -474,6 +478,7 @@ extern "C" int dx_embed_pos_fwd(const int64_t* ids, const float* table, const fl
                                 float* out, int B, int N, int C, void* stream) {
   DX_REQUIRE(ids && table && pos_table && lengths && out, DX_ERR_ARG, "dx_embed_pos_fwd: null pointer");
   DX_REQUIRE(C == C128, DX_ERR_UNSUPPORTED, "dx_embed_pos_fwd: C=%d (only 128)", C);
+  DX_REQUIRE(B > 0 && N > 0, DX_ERR_SHAPE, "dx_embed_pos_fwd: empty shape");
   const long rows = (long)B * N;
   hipLaunchKernelGGL(embed_pos_fwd_kernel, dim3((unsigned)((rows + 1) / 2)), dim3(256), 0, (hipStream_t)stream, ids, table,
                      pos_table, lengths, out, N, rows);
@@ -484,6 +489,7 @@ extern "C" int dx_embed_pos_bwd(const int64_t* ids, const float* dout, const int
                                 int N, int C, void* stream) {
   DX_REQUIRE(ids && dout && lengths && dtable, DX_ERR_ARG, "dx_embed_pos_bwd: null pointer");
   DX_REQUIRE(C == C128, DX_ERR_UNSUPPORTED, "dx_embed_pos_bwd: C=%d (only 128)", C);
+  DX_REQUIRE(B > 0 && N > 0, DX_ERR_SHAPE, "dx_embed_pos_bwd: empty shape");
   const long rows = (long)B * N;
   hipLaunchKernelGGL(embed_pos_bwd_kernel, dim3((unsigned)((rows + 1) / 2)), dim3(256), 0, (hipStream_t)stream, ids, dout,
                      lengths, dtable, N, rows);
@@ -494,6 +500,7 @@ extern "C" int dx_embed_pos_bwd(const int64_t* ids, const float* dout, const int
 extern "C" int dx_masked_mean_fwd(const float* x, const int64_t* lengths, float* out, int B, int N, int C, void* stream) {
   DX_REQUIRE(x && lengths && out, DX_ERR_ARG, "dx_masked_mean_fwd: null pointer");
   DX_REQUIRE(C == C128, DX_ERR_UNSUPPORTED, "dx_masked_mean_fwd: C=%d (only 128)", C);
+  DX_REQUIRE(B > 0 && N > 0, DX_ERR_SHAPE, "dx_masked_mean_fwd: empty shape");
   hipLaunchKernelGGL(masked_mean_fwd_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, lengths, out, N);
   DX_LAUNCH_CHECK();
   return DX_OK;
@@ -501,6 +508,7 @@ extern "C" int dx_masked_mean_fwd(const float* x, const int64_t* lengths, float*
 extern "C" int dx_masked_mean_bwd(const float* dy, const int64_t* lengths, float* dx, int B, int N, int C, void* stream) {
   DX_REQUIRE(dy && lengths && dx, DX_ERR_ARG, "dx_masked_mean_bwd: null pointer");
   DX_REQUIRE(C == C128, DX_ERR_UNSUPPORTED, "dx_masked_mean_bwd: C=%d (only 128)", C);
+  DX_REQUIRE(B > 0 && N > 0, DX_ERR_SHAPE, "dx_masked_mean_bwd: empty shape");
   const long rows = (long)B * N;
   hipLaunchKernelGGL(masked_mean_bwd_kernel, dim3((unsigned)((rows + 1) / 2)), dim3(256), 0, (hipStream_t)stream, dy, lengths,
                      dx, N, rows);
@@ -513,7 +521,11 @@ extern "C" int dx_film_assemble_fwd(const float* g_raw, const float* b_raw, cons
   DX_REQUIRE(g_raw && b_raw && film_enc && film_pp && film_dec && nb && ch, DX_ERR_ARG, "dx_film_assemble_fwd: null pointer");
   FilmArgs a{};
   a.g_raw = g_raw; a.b_raw = b_raw; a.post = post; a.film[0] = film_enc; a.film[1] = film_pp; a.film[2] = film_dec; a.B = B;
-  for (int m = 0; m < 3; ++m) { a.nb[m] = nb[m]; a.ch[m] = ch[m]; a.W += nb[m] * ch[m]; a.nblk += nb[m]; }
+  for (int m = 0; m < 3; ++m) {
+    DX_REQUIRE(nb[m] >= 0 && ch[m] >= 0, DX_ERR_SHAPE, "dx_film_assemble_fwd: negative layout entry");
+    a.nb[m] = nb[m]; a.ch[m] = ch[m]; a.W += nb[m] * ch[m]; a.nblk += nb[m];
+  }
+  DX_REQUIRE(B > 0 && a.W > 0, DX_ERR_SHAPE, "dx_film_assemble_fwd: empty shape");
   hipLaunchKernelGGL(film_assemble_fwd_kernel, dim3(grid_for((long)B * a.W)), dim3(256), 0, (hipStream_t)stream, a);
   DX_LAUNCH_CHECK();
   return DX_OK;
@@ -525,7 +537,11 @@ extern "C" int dx_film_assemble_bwd(const float* g_raw, const float* b_raw, cons
   FilmBwdArgs a{};
   a.g_raw = g_raw; a.b_raw = b_raw; a.post = post; a.dfilm[0] = dfilm_enc; a.dfilm[1] = dfilm_pp; a.dfilm[2] = dfilm_dec;
   a.dg_raw = dg_raw; a.db_raw = db_raw; a.dpost = post ? dpost : nullptr; a.B = B;
-  for (int m = 0; m < 3; ++m) { a.nb[m] = nb[m]; a.ch[m] = ch[m]; a.W += nb[m] * ch[m]; a.nblk += nb[m]; }
+  for (int m = 0; m < 3; ++m) {
+    DX_REQUIRE(nb[m] >= 0 && ch[m] >= 0, DX_ERR_SHAPE, "dx_film_assemble_bwd: negative layout entry");
+    a.nb[m] = nb[m]; a.ch[m] = ch[m]; a.W += nb[m] * ch[m]; a.nblk += nb[m];
+  }
+  DX_REQUIRE(B > 0 && a.W > 0, DX_ERR_SHAPE, "dx_film_assemble_bwd: empty shape");
   hipLaunchKernelGGL(film_assemble_bwd_kernel, dim3(grid_for((long)B * a.W)), dim3(256), 0, (hipStream_t)stream, a);
   DX_LAUNCH_CHECK();
   return DX_OK;
@@ -534,7 +550,7 @@ extern "C" int dx_film_assemble_bwd(const float* g_raw, const float* b_raw, cons
 extern "C" int dx_linear_small_fwd(const float* x, const float* w, const float* bias, float* y,
                                    const int64_t* mask_lengths, int N, long M, int K, int O, int relu, void* stream) {
   DX_REQUIRE(x && w && y, DX_ERR_ARG, "dx_linear_small_fwd: null pointer");
-  DX_REQUIRE(M > 0 && K > 0 && O > 0 && K % 4 == 0, DX_ERR_SHAPE, "dx_linear_small_fwd: bad shape M=%ld K=%d O=%d", M, K, O);
+  DX_REQUIRE(M > 0 && K > 0 && O > 0 && K % 4 == 0 && (!mask_lengths || N > 0), DX_ERR_SHAPE, "dx_linear_small_fwd: bad shape M=%ld K=%d O=%d N=%d", M, K, O, N);
   hipLaunchKernelGGL(linear_small_fwd_kernel, dim3(grid_for(M * O)), dim3(256), 0, (hipStream_t)stream, x, w, bias, y,
                      mask_lengths, N, M, K, O, relu);
   DX_LAUNCH_CHECK();
@@ -545,6 +561,7 @@ extern "C" int dx_linear_small_bwd(const float* dy, const float* y, const float*
                                    int relu, void* stream) {
   DX_REQUIRE(dy && x && w && dw, DX_ERR_ARG, "dx_linear_small_bwd: null pointer");
   DX_REQUIRE(!relu || y, DX_ERR_ARG, "dx_linear_small_bwd: relu needs the forward output y");
+  DX_REQUIRE(M > 0 && K > 0 && O > 0 && (!mask_lengths || N > 0), DX_ERR_SHAPE, "dx_linear_small_bwd: bad shape M=%ld K=%d O=%d N=%d", M, K, O, N);
   hipStream_t s = (hipStream_t)stream;
   const bool few_rows = !mask_lengths && M <= 512;   // M = batch size: LDS-tiled weight-gradient kernel
   if (dx) {
