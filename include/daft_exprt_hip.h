@@ -1228,6 +1228,46 @@ int dx_spectrogram_bwd(const float* wav, long ldw, const int64_t* n_samples, con
                        const float* window, const float* dmag, float* dwav, long lddw, void* ws, int B, int S, int T, int n_fft, int hop,
                        void* stream);
 
+/* ---- K37: one scale of a multi-scale mel loss -- the log10-mel of a waveform, and the L1 between it and a target's with its gradient
+ * back to the waveform (csrc/mel_loss.hip): the reconstruction term of BigVGAN-v2's fine-tuning.  Per scale it replaces what
+ * `vocoder_train.LossMel` + `mel_l1` are for the single HiFi-GAN mel: a dense (n_fft, 2 bins) DFT matmul, a filter-bank matmul, the
+ * log / clamp / abs torch ops and the autograd graph over them.  Additive entry points (the ABI version stays).
+ * wav (B, S) fp32, rows ldw floats apart; n_samples (B) int64 on the device and n_samples_host, the same B values on the host, as K36;
+ * window (n_fft) fp32 on the device, any table; twiddle (2 n_fft) fp32 from dx_mel_loss_tables (computed in double); fb (M, n_fft / 2 + 1)
+ * fp32 on the device, non-negative, filter m non-zero only on the bins [fb_lo[m], fb_hi[m]) (an empty filter: lo = hi); pad = p >= 0, the
+ * reflect padding per side (n_fft / 2 is torch.stft(center=True, pad_mode='reflect'), (n_fft - hop) / 2 HiFi-GAN's framing).
+ *     x~[s]     = x[r(s - p)],  s in [0, n + 2 p)                                    (torch's 'reflect', n = n_samples[b])
+ *     F_b       = 1 + (n + 2 p - n_fft) div hop
+ *     X[f, k]   = sum_j window[j] x~[f hop + j] exp(-2 pi i j k / n_fft),  k in [0, n_fft / 2];   mag = sqrt(re^2 + im^2)
+ *     mel[f, m] = sum_k fb[m, k] mag[f, k];   L[f, m] = log10(max(mel[f, m], eps))
+ * dx_mel_loss_log_mel writes L as log_mel (B, T, M) fp32, frame-major; frames F_b .. T are zeros.
+ * dx_mel_loss takes the generated waveform, target (B, T, M) from dx_mel_loss_log_mel and writes
+ *     loss[b]   = sum_{f < F_b, m} |target[b, f, m] - L[b, f, m]|                                                      (B) fp32
+ *     g[f, m]   = -sign(target - L) (mel >= eps ? 1 : 0) / (mel ln 10)         (sign(0) = 0: torch.abs's and torch.clamp's gradients)
+ *     dmag[f,k] = sum_m fb[m, k] g[f, m]        over [bin_lo[k], bin_hi[k]), a run of filters that holds every m with fb[m, k] != 0
+ *     G[f, k]   = dmag X / |X| (0 where |X| = 0);   dy_f[j] = window[j] Re sum_{k <= n_fft / 2} G[f, k] exp(+2 pi i j k / n_fft)
+ *     dx~[s]    = sum_{f : 0 <= s - f hop < n_fft} dy_f[s - f hop]
+ *     dwav[i]   = scale ( dx~[i + p] + (1 <= i <= p ? dx~[p - i] : 0) + (n - 1 - p <= i <= n - 2 ? dx~[p + 2 (n - 1) - i] : 0) )
+ *   dwav (B, S) fp32, rows lddw floats apart, zeros at and past n_samples[b]; log_mel, if not NULL, gets the generated waveform's L as
+ *   dx_mel_loss_log_mel writes it.  Samples at or past n_samples[b] and target frames at or past F_b are NEVER READ.  No atomics: frame
+ *   terms and windowed gradients go to ws -- dx_mel_loss_workspace(B, T, M, n_fft) bytes (0 for a non-positive argument), nothing in it has
+ *   to be initialised -- and are summed in an order the indices and n alone fix: two calls give the same bits, and an utterance gets the
+ *   same bits alone, in any batch and at any T.
+ * Checked on the host copy before any launch: n <= p or n + 2 p < n_fft (named by utterance), an n_fft outside {32, 64, 128, 256, 512,
+ * 1024, 2048}, a hop outside [1, n_fft], M < 1 and eps <= 0 return DX_ERR_UNSUPPORTED; n > S, F_b > T, ldw or lddw < S, B > 65535 or a
+ * non-positive B, S, T DX_ERR_SHAPE; a NULL pointer or a negative pad DX_ERR_ARG.  The kernels read the device copy and give an utterance
+ * that fails these conditions no frame at all.  fp32 throughout; n_fft / 4 threads per frame, 256 / (n_fft / 4) frames per workgroup below
+ * 1024 points. */
+int dx_mel_loss_tables(float* twiddle, int n_fft, void* stream);
+int dx_mel_loss_log_mel(const float* wav, long ldw, const int64_t* n_samples, const int64_t* n_samples_host, const float* twiddle,
+                        const float* window, const float* fb, const int* fb_lo, const int* fb_hi, float* log_mel, int B, int S, int T,
+                        int M, int n_fft, int hop, int pad, float eps, void* stream);
+long dx_mel_loss_workspace(int B, int T, int M, int n_fft);
+int dx_mel_loss(const float* wav, long ldw, const int64_t* n_samples, const int64_t* n_samples_host, const float* twiddle,
+                const float* window, const float* fb, const int* fb_lo, const int* fb_hi, const int* bin_lo, const int* bin_hi,
+                const float* target, float scale, float* loss, float* dwav, long lddw, float* log_mel, void* ws, int B, int S, int T, int M,
+                int n_fft, int hop, int pad, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 """Fine-tune a HiFi-GAN or BigVGAN vocoder on the fine-tuning data set, on the GPU
     python scripts/train_vocoder.py -ft FINE_TUNING_DATASET -cfg CONFIG_JSON -g G_CKPT [-do DO_CKPT] -o OUT_DIR [--steps 1000]
                                     [--batch_size 16] [--segment_size 8192] [--compute_dtype fp32] [--checkpoint_interval 500]
-                                    [--seed 1234] [--second_discriminator msd]
+                                    [--seed 1234] [--second_discriminator msd] [--mel_loss single]
 
   -ft    the `fine_tuning_dataset` directory `daft_exprt/fine_tune.py` writes: `<speaker>/<file>.npy` (teacher-forced mel) and
          `<speaker>/<file>.wav` (the cropped recording) per utterance
@@ -16,6 +16,11 @@
          the config's `resolutions`, default [[1024, 120, 600], [2048, 240, 1200], [512, 50, 240]]) under BigVGAN's recipe: the config's
          `learning_rate` (default 1e-4) and `clip_grad_norm` (default 1000).  `do_%08d` then holds `mrd` in place of `msd`; that an
          upstream BigVGAN `do_` file loads has not been verified
+  --mel_loss  the reconstruction term, independent of --second_discriminator: `single`, HiFi-GAN's L1 between two log-mels at the config's
+         `n_fft`, weighted 45, or `multiscale`, BigVGAN-v2's sum over seven STFT resolutions of the L1 between log10-mels (window lengths
+         `mel_loss_window_lengths`, default 32 ... 2048, with `mel_loss_n_mels`, default 5 ... 320, bands; weight `lambda_melloss`,
+         default 15), one fused HIP kernel pair per resolution.  The scale list and the weight are restated from the papers and have not
+         been checked against upstream's code
   -o     directory the checkpoints `g_%08d` / `do_%08d`, a copy of `config.json` and `vocoder_report.json` are written to;
          `scripts/synthesize.py -voc OUT_DIR/g_%08d` reads the result
 
@@ -51,6 +56,8 @@ def parse_args(argv=None):
     parser.add_argument('--seed', type=int, default=1234, help='seed of the segments and the discriminators')
     parser.add_argument('--second_discriminator', default='msd', choices=['msd', 'mrd'],
                         help="beside the MPD: HiFi-GAN's multi-scale (msd) or BigVGAN's multi-resolution (mrd) discriminator")
+    parser.add_argument('--mel_loss', default='single', choices=['single', 'multiscale'],
+                        help="the reconstruction term: HiFi-GAN's one log-mel (single) or BigVGAN-v2's seven resolutions (multiscale)")
     return parser.parse_args(argv)
 
 
@@ -72,6 +79,9 @@ def check_args(args):
         V.validate_config(config)
         trainable_config(config)
         LossMel(config)
+        if args.mel_loss == 'multiscale':
+            from daft_exprt.mel_loss import MultiScaleMelLoss
+            MultiScaleMelLoss(config).check_segment(args.segment_size)
     except (ValueError, json.JSONDecodeError) as e:
         raise SystemExit(f'train_vocoder.py: {args.config}: {e}')
     if args.segment_size % int(config['hop_size']):
@@ -90,7 +100,7 @@ def main(argv=None):
         report = fine_tune_vocoder(config, args.fine_tuning_dataset, args.generator, args.discriminators, out_dir=args.output_dir,
                                    steps=args.steps, batch_size=args.batch_size, segment_size=args.segment_size,
                                    compute_dtype=args.compute_dtype, checkpoint_interval=args.checkpoint_interval, seed=args.seed,
-                                   second_discriminator=args.second_discriminator)
+                                   second_discriminator=args.second_discriminator, mel_loss=args.mel_loss)
     except ValueError as e:                      # a mel of another hop / bin count, a short data set, a foreign checkpoint
         raise SystemExit(f'train_vocoder.py: {e}')
     path = os.path.join(args.output_dir, 'vocoder_report.json')

@@ -20,7 +20,13 @@ gradient clipping) beside the step against MPD + MSD, and per resolution the spe
 `dx_spectrogram_bwd` with its gather launch), 20 calls per timed window, against `torch.stft` + `torch.norm` + autograd on the same
 device and waveforms -- a yardstick that lives here only -- and the share of a step that K36 takes: per resolution four forwards (y and
 y_hat in either half of the step) and one backward.
-Run:  python tools/bench_vocoder_train.py [--reps 5] [--batch 16] [--segment 8192] [--bigvgan] [--mrd]
+
+`--mel_loss` adds, under "mel_loss", the fp32 step (MPD + MSD) with HiFi-GAN's single mel loss and with BigVGAN-v2's multi-scale one
+(`mel_loss.MultiScaleMelLoss`, K37) from the same run, and per scale, 20 calls per timed window: the entry points alone on buffers
+allocated once (`dx_mel_loss_log_mel` of the recording + `dx_mel_loss` of the synthesis: three launches), the same through the Python
+wrappers with the autograd backward (`log_mel` + `log_mel_l1` + `.backward()`), and `torch.stft` + filter bank + log10 + L1 + autograd
+on the same device and waveforms -- a yardstick that lives here only.
+Run:  python tools/bench_vocoder_train.py [--reps 5] [--batch 16] [--segment 8192] [--bigvgan] [--mrd] [--mel_loss]
 """
 import argparse
 import json
@@ -327,6 +333,79 @@ def mrd(args, cfg, sd, mel, audio, loss_mel, dev):
     return out
 
 
+def mel_loss(args, cfg, sd, mel, audio, loss_mel, dev):
+    ''' the "mel_loss" entry of the result '''
+    import ctypes
+    from daft_exprt import _hip as H
+    from daft_exprt import mel_loss as ML
+    from daft_exprt import vocoder_train as VT
+    out = {}
+    module = ML.MultiScaleMelLoss(cfg)
+    for kind, mod in (('single', None), ('multiscale', module)):
+        torch.manual_seed(0)
+        generator = VT.TrainableGenerator(cfg, sd, compute_dtype='fp32').to(dev)
+        mpd, msd = VT.MultiPeriodDiscriminator().to(dev), VT.MultiScaleDiscriminator().to(dev)
+        optim_g = torch.optim.AdamW(generator.parameters(), VT.LEARNING_RATE, betas=VT.ADAM_BETAS)
+        optim_d = torch.optim.AdamW(list(msd.parameters()) + list(mpd.parameters()), VT.LEARNING_RATE, betas=VT.ADAM_BETAS)
+        step = lambda: VT.train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio, mel_loss=mod)      # noqa: E731
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        out[f'{kind}_ms_per_step'] = _timed(step, args.reps)
+        del generator, mpd, msd, optim_g, optim_d
+        torch.cuda.empty_cache()
+    B, S = audio.shape
+    counts = [S] * B
+    y_hat = (audio + 0.05 * torch.randn_like(audio)).contiguous()
+    entries, launches_ms, call_ms = [], 0., 0.
+    for s in module.scales:
+        T, M = s.frames(S), s.n_mels
+        factor = 1. / (M * B * T)
+        tw, win, fb, fb_lo, fb_hi, bin_lo, bin_hi = s.tables(dev)
+        nd, nh = torch.tensor(counts, dtype=torch.int64, device=dev), (ctypes.c_int64 * B)(*counts)
+        target, loss, dwav = torch.empty((B, T, M), device=dev), torch.empty((B,), device=dev), torch.empty((B, S), device=dev)
+        ws = torch.empty((H.lib().dx_mel_loss_workspace(B, T, M, s.n_fft) // 4,), device=dev)
+        x = y_hat.clone().requires_grad_(True)
+        window = win.clone()
+
+        def launches():
+            H.check(H.lib().dx_mel_loss_log_mel(H.ptr(audio), S, H.ptr(nd), ctypes.addressof(nh), H.ptr(tw), H.ptr(win), H.ptr(fb),
+                                                H.ptr(fb_lo), H.ptr(fb_hi), H.ptr(target), B, S, T, M, s.n_fft, s.hop, s.pad, s.eps, H.stream()))
+            H.check(H.lib().dx_mel_loss(H.ptr(y_hat), S, H.ptr(nd), ctypes.addressof(nh), H.ptr(tw), H.ptr(win), H.ptr(fb), H.ptr(fb_lo),
+                                        H.ptr(fb_hi), H.ptr(bin_lo), H.ptr(bin_hi), H.ptr(target), factor, H.ptr(loss), H.ptr(dwav), S, None,
+                                        H.ptr(ws), B, S, T, M, s.n_fft, s.hop, s.pad, s.eps, H.stream()))
+
+        def calls():
+            x.grad = None
+            ML.log_mel_l1(x, ML.log_mel(audio, counts, s), counts, s, factor).backward()
+
+        def torch_log_mel(w):
+            spec = torch.stft(w, s.n_fft, hop_length=s.hop, win_length=s.n_fft, window=window, center=True, pad_mode='reflect',
+                              return_complex=True)
+            return torch.log10(torch.clamp(fb @ spec.abs(), min=s.eps))
+
+        def yardstick():
+            x.grad = None
+            with torch.no_grad():
+                t = torch_log_mel(audio)
+            F.l1_loss(torch_log_mel(x), t).backward()
+        assert tuple(torch_log_mel(audio).shape) == (B, M, T)
+        ms = {}
+        for name, fn in (('k37_launches', launches), ('k37_calls_with_autograd', calls), ('torch_stft_autograd', yardstick)):
+            fn()
+            fn()
+            torch.cuda.synchronize()
+            ms[name + '_ms'] = _timed(lambda fn=fn: [fn() for _ in range(LAUNCHES)], args.reps) / LAUNCHES
+        ms['speedup_of_the_calls'] = ms['torch_stft_autograd_ms'] / ms['k37_calls_with_autograd_ms']
+        launches_ms += ms['k37_launches_ms']
+        call_ms += ms['k37_calls_with_autograd_ms']
+        entries.append(dict({'n_fft': s.n_fft, 'hop': s.hop, 'n_mels': M, 'frames_per_batch': B * T}, **ms))
+    out['scales'] = entries
+    out['k37_launches_ms_per_step'], out['k37_calls_ms_per_step'] = launches_ms, call_ms
+    out['k37_calls_share_of_step'] = call_ms / out['multiscale_ms_per_step']
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
@@ -334,6 +413,7 @@ def main():
     ap.add_argument('--segment', type=int, default=8192)
     ap.add_argument('--bigvgan', action='store_true', help='also measure a BigVGAN generator of the base layout (V1 + snakebeta)')
     ap.add_argument('--mrd', action='store_true', help="also measure the step against BigVGAN's multi-resolution discriminator and K36")
+    ap.add_argument('--mel_loss', action='store_true', help="also measure the step with BigVGAN-v2's multi-scale mel loss and K37")
     args = ap.parse_args()
     warnings.simplefilter('ignore')
     from daft_exprt import vocoder_train as VT
@@ -390,6 +470,8 @@ def main():
         out['bigvgan'] = bigvgan(args, cfg, mel, proj, lengths, dev)
     if args.mrd:
         out['mrd'] = mrd(args, cfg, sd, mel, audio, loss_mel, dev)
+    if args.mel_loss:
+        out['mel_loss'] = mel_loss(args, cfg, sd, mel, audio, loss_mel, dev)
     print(json.dumps(out))
 
 

@@ -681,6 +681,7 @@ def load_discriminator_state(do_checkpoint, mpd, msd, optim_g=None, optim_d=None
 # ---- training -------------------------------------------------------------------------------------------------------------------
 
 LEARNING_RATE, ADAM_BETAS, LR_DECAY = 2e-4, (0.8, 0.99), 0.999
+MEL_LOSSES = ('single', 'multiscale')       # the reconstruction term: HiFi-GAN's one log-mel, or BigVGAN-v2's seven (mel_loss.py, K37)
 MRD_LEARNING_RATE, MRD_CLIP_GRAD_NORM = 1e-4, 1000.      # BigVGAN's recipe (Lee et al. 2023, appendix), where the config gives none
 
 
@@ -689,10 +690,12 @@ def _clip(optimizer, max_norm):
         torch.nn.utils.clip_grad_norm_([p for group in optimizer.param_groups for p in group['params']], max_norm)
 
 
-def train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio, clip_grad_norm=None):
+def train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio, clip_grad_norm=None, mel_loss=None):
     ''' one step of HiFi-GAN's training: the discriminators on the detached synthesis, then the generator.  `msd` is the second
         discriminator, multi-scale or multi-resolution; `clip_grad_norm` (BigVGAN's recipe) clips the gradient norm of each optimiser's
-        parameters before its step.  Returns {'disc', 'adv', 'fm', 'mel'} as device scalars (mel = the unweighted L1 of the log-mels) '''
+        parameters before its step.  `mel_loss`: None, the L1 of `loss_mel`'s log-mels weighted MEL_LOSS_WEIGHT, or a module such as
+        `mel_loss.MultiScaleMelLoss` (K37) whose value of (audio, synthesis) and whose `weight` take their place.
+        Returns {'disc', 'adv', 'fm', 'mel'} as device scalars (mel = the unweighted reconstruction term) '''
     B, _, frames = mel.shape
     lengths = torch.full((B,), frames, dtype=torch.int64, device=mel.device)
     y = audio[:, None]
@@ -706,13 +709,18 @@ def train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio, clip
     _clip(optim_d, clip_grad_norm)
     optim_d.step()
     optim_g.zero_grad(set_to_none=True)
-    l_mel = mel_l1(loss_mel(audio), loss_mel(y_hat[:, 0]))
+    if mel_loss is None:
+        l_mel = mel_l1(loss_mel(audio), loss_mel(y_hat[:, 0]))
+        mel_weight = MEL_LOSS_WEIGHT
+    else:
+        l_mel = mel_loss(audio, y_hat[:, 0])
+        mel_weight = mel_loss.weight
     l_adv, l_fm = 0., 0.
     for disc in (mpd, msd):
         _, fake, fmap_r, fmap_g = disc(y, y_hat)
         l_adv = l_adv + generator_adversarial_loss(fake)
         l_fm = l_fm + feature_matching_loss(fmap_r, fmap_g)
-    (l_adv + l_fm + MEL_LOSS_WEIGHT * l_mel).backward()
+    (l_adv + l_fm + mel_weight * l_mel).backward()
     _clip(optim_g, clip_grad_norm)
     optim_g.step()
     return {'disc': loss_d.detach(), 'adv': l_adv.detach(), 'fm': l_fm.detach(), 'mel': l_mel.detach()}
@@ -744,17 +752,22 @@ def held_out_mel_l1(config, state_dict, held_out, compute_dtype, device, centere
 
 def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, out_dir=None, steps=1000, batch_size=16,
                       segment_size=8192, compute_dtype='fp32', checkpoint_interval=500, log_interval=50, validation_fraction=10,
-                      seed=1234, device=None, centered=True, second_discriminator='msd'):
+                      seed=1234, device=None, centered=True, second_discriminator='msd', mel_loss='single'):
     ''' fine-tunes the generator of `g_checkpoint` on a `fine_tuning_dataset` (single GPU) and writes `g_%08d` / `do_%08d` /
         `config.json` to `out_dir` at every checkpoint interval and at the end.  AdamW, lr 2e-4, betas (0.8, 0.99), decayed by 0.999
         per epoch; the discriminator step before the generator step.  Without `do_checkpoint` the discriminators start from their
         initialisation (a warning).  `second_discriminator`: 'msd', HiFi-GAN's recipe as above for either generator family, or 'mrd',
         BigVGAN's: MPD + the multi-resolution discriminator (`bigvgan_train.MultiResolutionDiscriminator`, over K36), the config's
         `learning_rate` (default 1e-4) and `clip_grad_norm` (default 1000, on both optimisers' parameters before their step), the same
-        betas and decay; `do_%08d` then holds 'mrd' in place of 'msd'.  Returns the report `scripts/train_vocoder.py` writes. '''
+        betas and decay; `do_%08d` then holds 'mrd' in place of 'msd'.  `mel_loss`: 'single', HiFi-GAN's one log-mel weighted 45
+        (`LossMel`), or 'multiscale', BigVGAN-v2's sum over seven resolutions weighted 15 (`mel_loss.MultiScaleMelLoss`, over K37);
+        independent of `second_discriminator`, and held-out validation is the same either way.  Returns the report
+        `scripts/train_vocoder.py` writes. '''
     config = V.load_config(config)
     V.validate_config(config)
     _second_key(second_discriminator)
+    if mel_loss not in MEL_LOSSES:
+        raise ValueError(f'mel_loss is {mel_loss!r}, expected "single" or "multiscale"')
     device = H.device(device)
     hop = int(config['hop_size'])
     if segment_size < hop or segment_size % hop:
@@ -767,6 +780,11 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
         raise ValueError(f'{g_checkpoint}: no "generator" entry (expected a HiFi-GAN generator checkpoint)')
     torch.manual_seed(seed)
     loss_mel = LossMel(config).to(device)
+    multiscale = None
+    if mel_loss == 'multiscale':
+        from daft_exprt.mel_loss import MultiScaleMelLoss
+        multiscale = MultiScaleMelLoss(config)
+        multiscale.check_segment(segment_size)
     generator = trainable_generator(config, ckpt['generator'], compute_dtype=compute_dtype).to(device)
     lr, clip = LEARNING_RATE, None
     if second_discriminator == 'mrd':
@@ -790,7 +808,7 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
     report = {'utterances_used': len(train), 'utterances_skipped': skipped, 'utterances_held_out': len(held_out),
               'generator_family': 'bigvgan' if V.is_bigvgan(config) else 'hifi-gan', 'compute_dtype': compute_dtype,
               'batch_size': batch_size, 'segment_size': segment_size, 'first_step': first_step,
-              'second_discriminator': second_discriminator, 'log': []}
+              'second_discriminator': second_discriminator, 'mel_loss': mel_loss, 'log': []}
     validate = lambda: held_out_mel_l1(config, generator.state_dict(), held_out, compute_dtype, device, centered)   # noqa: E731
     report['held_out_mel_l1_start'] = validate()
     step, epoch, last_val = first_step, max(sampler.epoch, 1), report['held_out_mel_l1_start']
@@ -799,7 +817,7 @@ def fine_tune_vocoder(config, data_set_dir, g_checkpoint, do_checkpoint=None, ou
     with torch.cuda.device(device):
         while step < first_step + steps:
             mel, audio = sampler.draw(batch_size)
-            losses = train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio, clip_grad_norm=clip)
+            losses = train_step(generator, mpd, msd, optim_g, optim_d, loss_mel, mel, audio, clip_grad_norm=clip, mel_loss=multiscale)
             step += 1
             while epoch < sampler.epoch:                              # the decay of an epoch that ended with this batch's draw
                 sched_g.step()
